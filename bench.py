@@ -3,7 +3,16 @@ N MI355X of one node, one process per GPU (RCCL all-reduce of the hallucination-
 resident in HBM.  Prints ONE JSON line (rank 0).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times `--steps` steps and prints the line (`value`, `ms_per_step`, ...): nothing else.  `--full` adds
+the measurements that take runs of their own, after the timed steps (rank 0, N=1 where noted): the PCIe-inclusive rate, the
+`roofline` object and the `cpu_baseline` object below (`--no-roofline` / `--no-cpu-baseline` leave one of them out).
+`--dump-outputs DIR`: after the timed steps, what the last of them computed -> DIR/<name>.npy (float32 / float64, a fixed seeded
+sample of the parameter and gradient arenas; the inputs are the same seeded synthetic batch in every run), so that two builds can be
+compared output for output.
 
 `roofline`: the dominant kernel is the convolution behind hd_conv2d (the conv_igemm / conv3x3_w8 / conv3x3_small kernels: every
 conv / data-gradient / FC of the U-Net and the detector).  `achieved` = algorithmic FLOPs of the launches of ONE real
@@ -11,7 +20,7 @@ training step / the duration of those launches replayed once each, in step order
 number a rocprofv3 kernel summary of the step reproduces; `achieved_isolated` re-issues every launch 5x back to back (warm caches:
 the upper bound the first round quoted).  `mfma_util` / `traffic` come from the rocprofv3 PMC passes committed under profiles/.
 `cpu_baseline`: the CPU oracle (oracle/step.py, "port") on this host's cores (rank 0, N=1 only): batch 8, all cores, one warm-up
-(batch 2) + one timed step, plus the U-Net alone at the reference's 8 threads -- bounded so that the default run stays within
+(batch 2) + one timed step, plus the U-Net alone at the reference's 8 threads -- bounded so that a `--full` run stays within
 minutes; `--cpu-protocol full` runs SURVEY 8d's protocol (2 warm-ups + 3 timed steps at batch 8, 8 threads and all cores).
 Other BASELINE configs: `--config retinanet16` (configs[3]) and `--config detector16` (configs[4]) print their own lines.
 """
@@ -92,6 +101,44 @@ def _flush_c_stdio():
         ctypes.CDLL(None).fflush(None)
     except Exception:
         pass
+
+
+DUMP_SAMPLE = 1 << 22            # elements kept of an arena larger than this (4 Mi fp32 = 16 MiB per array)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _sample(flat, idx):
+    """A fixed sample of a flat tensor (`idx`: _sample_index of its size, None = all of it) -> float32 numpy."""
+    flat = flat.detach().reshape(-1)
+    if idx is not None:
+        flat = flat[idx.to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def _sample_index(n, seed=0):
+    """DUMP_SAMPLE seeded positions out of n, ascending (the same in every run on an arena of n elements); None when n fits."""
+    if n <= DUMP_SAMPLE:
+        return None
+    return torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:DUMP_SAMPLE].sort().values
+
+
+def dump_outputs(dirname, loss, arena, buffers=()):
+    """--dump-outputs: what the last timed step computed -> DIR/<name>.npy.  `loss`: the value fit_step returned (float64);
+    `params` / `grads`: the same seeded sample of the parameter arena after the update and of the (loss-scaled) gradient arena the
+    update consumed; `buffers`: the floating-point buffers (BatchNorm running statistics) after the step, concatenated."""
+    import numpy as np
+    idx = _sample_index(arena.flat_params.numel())
+    arrays = {"loss": np.array([float(loss)], dtype=np.float64),
+              "params": _sample(arena.flat_params, idx), "grads": _sample(arena.flat_grads, idx)}
+    bufs = [b.detach().reshape(-1).float() for b in buffers if b.is_floating_point()]
+    if bufs:
+        arrays["buffers"] = torch.cat(bufs).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def conv_roofline(lit, batch, reps=5, peak=None):
@@ -420,6 +467,8 @@ def bench_detector_training(args, dev, rank, world):
         param_drift = float(drift)
     if not torch.isfinite(loss):
         raise SystemExit("non-finite loss in the timed region")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, lit.arena)
     if rank == 0:
         print(json.dumps({
             "ms_per_step_by_rank": per_rank_ms, "max_parameter_difference_between_ranks": (param_drift if dist.is_initialized() else None),
@@ -440,8 +489,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the PCIe-inclusive rate, the conv roofline and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline")
     ap.add_argument("--detector", default="fasterrcnn", choices=["fasterrcnn", "retinanet"],
                     help="fasterrcnn = the configuration BASELINE.json's metric is quoted on (default); retinanet = configs[3]")
     ap.add_argument("--batch", type=int, default=0, help="images per GPU (default 8: BASELINE configs[1])")
@@ -453,6 +506,8 @@ def main():
                     help="16 = BASELINE configs[1] (the headline); 32 = the reference's default --precision 32: fp32 storage and VALU "
                          "arithmetic end to end (the parity mode, untuned).  Its own JSON line, without the fp16 roofline")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     global BATCH_PER_GPU
     if args.config == "retinanet16":
         args.detector, args.batch = "retinanet", args.batch or 16
@@ -584,6 +639,8 @@ def main():
     if not torch.isfinite(loss):
         raise SystemExit("non-finite loss in the timed region")
     lit.optimizer.resolve_found_inf()          # the last timed step's overflow flag (skipped_steps below must include it)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, lit.encoder_decoder.runner, lit.encoder_decoder.buffers())
 
     if rank == 0:
         # everything below is rank-0-only measurement: no collective may be issued from here on (the other ranks are
@@ -631,7 +688,7 @@ def main():
                                 # per bucket, issue order: the part of its all-reduce the backward pass did not hide (HIP events on
                                 # the compute stream around the wait), mean over the timed steps of rank 0
                                 "exposed_wait_per_bucket": lit.averager.exposed_wait_ms()}
-        if world == 1:
+        if args.full and world == 1:
             # PCIe-inclusive rate (never `value`): every step's batch comes from host memory through the product's input path
             # (hallucidet_amd.dataloader.DevicePrefetcher: uint8 images stacked into pinned memory, copied on a side HIP stream
             # while the previous step computes, divided by 255 on the GPU) -- reference: the DataLoader -> .to(device) of pl.Trainer
@@ -658,9 +715,9 @@ def main():
             # which protocol `value` follows: the bench contract asks for inputs resident in HBM when the timed region starts; SURVEY 8d
             # words the metric H2D-inclusive -- that rate is the key above, never `value`
             out["value_protocol"] = "inputs resident in HBM (bench contract); H2D-inclusive rate of SURVEY 8d: pcie_inclusive_images_per_s"
-        if not args.no_roofline and args.detector == "fasterrcnn" and BATCH_PER_GPU == 8:
+        if args.full and not args.no_roofline and args.detector == "fasterrcnn" and BATCH_PER_GPU == 8:
             out["roofline"] = conv_roofline(lit, batch, peak=MFMA_F32_PEAK_TFLOPS if args.precision == 32 else None)
-        if world == 1 and not args.no_cpu_baseline and not args.config:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.config:
             out["cpu_baseline"] = cpu_baseline(args.cpu_protocol)
         _flush_c_stdio()               # RCCL's version banner sits in C stdio's buffer when stdout is a pipe: out with it BEFORE the line
         print(json.dumps(out), flush=True)

@@ -215,10 +215,10 @@ def tame_detector_(model):
             m.bn1.weight.fill_(0.9)
 
 
-def gen_glue(ref):
+def gen_glue(ref, seed=7, name="glue_fasterrcnn.npz"):
     """Drive the REFERENCE's eval_forward_fasterrcnn.py over the oracle's duck-typed detector: pins call order,
     argument contract, loss keys and detection post-processing of the reference glue."""
-    model, images, targets, perm_log, g = make_detector_case()
+    model, images, targets, perm_log, g = make_detector_case(seed=seed)
     losses, dets = ref.glue.eval_forward_fasterrcnn(model, images, targets, train_det=False)
     blob = {"images": images, "n_perm": torch.tensor(len(perm_log))}
     for i, t in enumerate(targets):
@@ -228,7 +228,7 @@ def gen_glue(ref):
     for i, d in enumerate(dets):
         for k, v in d.items():
             blob["det%d.%s" % (i, k)] = v.detach()
-    np.savez_compressed(os.path.join(OUT, "glue_fasterrcnn.npz"), **{k: v.numpy() for k, v in blob.items()})
+    np.savez_compressed(os.path.join(OUT, name), **{k: v.numpy() for k, v in blob.items()})
 
 
 def make_retinanet_case(seed=13, n_img=2, H=96, W=128):
@@ -329,6 +329,7 @@ def main():
     gen_transform(ref)
     gen_config(ref)
     gen_glue(ref)
+    gen_glue(ref, seed=11, name="glue_fasterrcnn_seed11.npz")
     gen_glue_retinanet(ref)
     gen_glue_fcos(ref)
     for f in sorted(os.listdir(OUT)):

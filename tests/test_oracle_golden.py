@@ -145,18 +145,21 @@ def test_oracle_orchestration_equals_reference_glue():
         assert d["boxes"].shape[0] <= 100 and d["labels"].dtype == torch.int64
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="reference tree only exists in the build container")
 def test_reference_glue_live():
+    """A second case (seed 11) of the reference's eval_forward_fasterrcnn.py over the oracle detector: the fixture holds what the
+    reference's glue returned on it (tests/golden/make_golden.py), the oracle's own orchestration must reproduce it."""
     mg = _mg()
-    ref = mg.load_reference()
+    z = npz("glue_fasterrcnn_seed11.npz")
     model, images, targets, _, _ = mg.make_detector_case(seed=11)
-    l_ref, d_ref = ref.glue.eval_forward_fasterrcnn(model, images, targets, train_det=False)
-    model2, images2, targets2, _, _ = mg.make_detector_case(seed=11)
-    l_or, d_or = od.eval_forward_fasterrcnn(model2, images2, targets2, train_det=False)
+    assert torch.equal(images, z["images"])
+    l_or, d_or = od.eval_forward_fasterrcnn(model, images, targets, train_det=False)
+    l_ref = {k[len("loss."):]: v for k, v in z.items() if k.startswith("loss.")}
+    assert set(l_ref) == set(l_or) and len(l_ref) == 4
     for k in l_ref:
         assert torch.allclose(l_ref[k], l_or[k], rtol=1e-6, atol=1e-7), k
-    for a, b in zip(d_ref, d_or):
-        assert torch.equal(a["labels"], b["labels"]) and torch.allclose(a["boxes"], b["boxes"], atol=1e-5)
+    assert len(d_or) == 2
+    for i, b in enumerate(d_or):
+        assert torch.equal(z["det%d.labels" % i], b["labels"]) and torch.allclose(z["det%d.boxes" % i], b["boxes"], atol=1e-5)
 
 
 # ---------------------------------------------------------------------------------- RetinaNet (config 4)

@@ -162,3 +162,31 @@ def test_bench_detector16_distributed_branch_runs_at_world_size_one(dev, monkeyp
                                 {"HD_FORCE_DIST": "1", "MASTER_PORT": _free_port(), "MASTER_ADDR": "127.0.0.1"})
     assert out["n_gpus"] == 1 and out["max_parameter_difference_between_ranks"] == 0.0
     assert len(out["ms_per_step_by_rank"]) == 1 and out["skipped_steps"] == 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(dev, monkeypatch, capsys, tmp_path):
+    """A plain `bench.py` run prints the headline line and nothing that needs runs of its own (PCIe-inclusive rate, roofline, CPU
+    baseline: `--full`); `--steps` is the number of timed steps; `--dump-outputs DIR` writes what the last timed step computed --
+    the loss it returned, seeded samples of the parameter / gradient arenas, the BatchNorm buffers -- as float arrays within 64 MB."""
+    import numpy as np
+    d = tmp_path / "dump"
+    out = _run_bench_in_process(monkeypatch, capsys, ["--steps", "3", "--warmup", "1", "--dump-outputs", str(d)], {})
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["skipped_steps"] == 0
+    assert out["metric"].startswith("images/sec") and out["unit"] == "images/s" and out["higher_is_better"] is True and out["dtype"] == "f16"
+    assert not {"roofline", "cpu_baseline", "pcie_inclusive_images_per_s"} & set(out), sorted(out)
+    arrays = {f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))}
+    assert set(arrays) == {"loss", "params", "grads", "buffers"}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays["params"].shape == arrays["grads"].shape == (1 << 22,)
+    assert abs(float(arrays["loss"][0]) - out["final_loss"]) <= 1e-5
+    assert np.abs(arrays["grads"]).max() > 0
+
+
+def test_bench_full_adds_its_own_measurements(dev, monkeypatch, capsys):
+    """`--full` runs the legs a plain run leaves out, after the timed steps: the PCIe-inclusive rate and the conv roofline (the CPU
+    baseline is left out here with --no-cpu-baseline: it takes minutes of CPU time)."""
+    out = _run_bench_in_process(monkeypatch, capsys, ["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"], {})
+    assert out["steps"] == 2 and out["pcie_inclusive_images_per_s"] > 0 and "cpu_baseline" not in out
+    r = out["roofline"]
+    assert r["launches_per_step"] > 100 and 0 < r["frac"] < 1
