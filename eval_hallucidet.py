@@ -18,10 +18,12 @@ def main(argv=None):
     torch.manual_seed(args.seed)
     dataset = args.dataset or "llvip"
     Config.set_detector(args.detector, train_det=False, pretrained=args.directly_coco, dataset=dataset)
+    Config.set_loss_weights(args)        # eval_hallucidet.py:39: the test loss (and val_loss) carry the same weighted terms as training
     dev = args.device if args.device not in (None, "gpu") else "cuda"
     dm = MultiModalDataModule(dataset, args.test, args.test, args.test, args.test, batch_size=args.batch, num_workers=args.num_workers,
                               ext=args.ext or ".jpg", seed=args.seed)
-    kw = dict(batch_size=args.batch, model_name=args.decoder_backbone, detector_name=Config.Detector.name, precision=args.precision, device=dev)
+    kw = dict(batch_size=args.batch, model_name=args.decoder_backbone, detector_name=Config.Detector.name, precision=args.precision, device=dev,
+              loss_pixel=Config.Losses.pixel, loss_perceptual=Config.Losses.perceptual)
     model = EncoderDecoderLit.load_from_checkpoint(args.hallucidet_path, strict=False, **kw) if args.hallucidet_path else EncoderDecoderLit(**kw)
     if args.detector_path:
         from hallucidet_amd.checkpoint import load_detector

@@ -21,6 +21,7 @@ import warnings
 
 import torch
 
+from . import ops
 from .utils import eval_forward_fasterrcnn as _eff
 from .models.detection import LazyDetections, _PAD_IDX_CACHE
 from .segmentation_models.unet import capture_without_gc
@@ -190,6 +191,13 @@ class DetectorStepGraph:
                         d.flush()
             (dimg,) = torch.autograd.grad(total, x, grad_outputs=e.scale)      # = d(total * scale)/dx without the extra launches
             cur.wait_stream(branch)
+            if e.pixel is not None:
+                # the pixel loss (train_hallucidet.py:173-176,209): both weighted terms, total = (det_total + rgb) + ir, and their scaled
+                # gradient added into dimg -- the buffer the U-Net's backward graphs adopt -- in one launch pair
+                kind, w_rgb, w_ir = e.pixel
+                out = ops.pixel_loss(e.x, e.rgb, e.ir, kind, w_rgb, w_ir, base_total=total, gs=e.scale, dhall=dimg)
+                losses_det = dict(losses_det, pixel_rgb=out[0], pixel_ir=out[1], det_total=total)
+                total = out[2]
             return losses_det, total, dets, dimg
 
         _eff._GRAPH_FLAGS = []
@@ -234,6 +242,9 @@ class DetectorStepGraph:
         alias = imgs_hallucinated.data_ptr() if self._aliased_runner(imgs_hallucinated) is not None else 0
         key = (tuple(imgs_hallucinated.shape), alias, tuple(imgs_rgb.shape), tuple(imgs_ir.shape),
                imgs_ir.stride(1) == 0, G, w, lit.detector_name, bool(lit.detector.transform.training))
+        pixel = lit.pixel_setup()                      # (kind, w_rgb, w_ir) of the pixel loss, None when off (the key is then unchanged)
+        if pixel is not None:
+            key = key + (pixel,)
         e = self.entries.get(key)
         # the loss scale of this step: GradScaler order (the overflow check of step t decides the scale of step t+1), resolved
         # BEFORE the replay because the scaled backward pass is inside the graph
@@ -242,6 +253,7 @@ class DetectorStepGraph:
         fresh = e is None
         if fresh:
             e = self._build(key, imgs_hallucinated, imgs_rgb, imgs_ir, G)
+            e.pixel = pixel
         if e.scale_value != s:
             e.scale.fill_(s)
             e.inv_scale.fill_(1.0 / s)

@@ -1080,3 +1080,47 @@ def adam_step(p, g, m, v, *, lr, beta1, beta2, eps, weight_decay, clip_value, in
 
 def check_finite(g, found_inf):
     check(_abi.load().hd_check_finite(ptr(g), g.numel(), ptr(found_inf), _stream()), "hd_check_finite")
+
+
+PIXEL_KINDS = {"mse": 0, "l1": 1}
+_PIXEL_PART = 2048          # floats of hd_pixel_loss's partial-sum workspace
+
+
+def pixel_loss(hall, rgb, ir, kind, w_rgb, w_ir, *, base_total=None, gs=None, dhall=None, out=None):
+    """hd_pixel_loss: -> (w_rgb * L(hall, rgb), w_ir * L(hall, ir)[, base_total + both]) as one fp32 tensor, on the current stream; the
+    third element only when `base_total` is given.  L = MSE or L1 mean over N*3*H*W.  hall / rgb: fp32 contiguous [N, 3, H, W]; ir: fp32
+    contiguous [N, 1, H, W] (one plane, broadcast over the channels) or [N, 3, H, W].  Gradient mode (`dhall`, same layout as hall):
+    dhall += gs * d(out[0] + out[1]) / d hall, `gs` a 0-dim fp32 device tensor.  Nothing is broadcast or converted here: any other
+    shape, dtype or layout raises."""
+    k = PIXEL_KINDS.get(kind, kind) if isinstance(kind, str) else kind
+    if k not in (0, 1):
+        raise ValueError("pixel_loss: kind must be 'mse' or 'l1' (got %r)" % (kind,))
+    _need_cuda(hall, rgb, ir, base_total, gs, dhall, out)
+    if hall.dim() != 4 or hall.shape[1] != 3:
+        raise ValueError("pixel_loss: hall must be [N, 3, H, W] (got %s)" % (tuple(hall.shape),))
+    N, _, H, W = hall.shape
+    if tuple(rgb.shape) != tuple(hall.shape):
+        raise ValueError("pixel_loss: rgb must have hall's shape %s (got %s)" % (tuple(hall.shape), tuple(rgb.shape)))
+    if ir.dim() != 4 or ir.shape[1] not in (1, 3) or (ir.shape[0], ir.shape[2], ir.shape[3]) != (N, H, W):
+        raise ValueError("pixel_loss: ir must be [%d, 1 or 3, %d, %d] (got %s)" % (N, H, W, tuple(ir.shape)))
+    named = [("hall", hall), ("rgb", rgb), ("ir", ir)] + ([("dhall", dhall)] if dhall is not None else [])
+    for name, t in named:
+        if t.dtype != torch.float32:
+            raise TypeError("pixel_loss: %s must be float32 (got %s)" % (name, t.dtype))
+        if not t.is_contiguous():
+            raise ValueError("pixel_loss: %s must be contiguous (strides %s)" % (name, tuple(t.stride())))
+    if dhall is not None:
+        if tuple(dhall.shape) != tuple(hall.shape):
+            raise ValueError("pixel_loss: dhall must have hall's shape %s (got %s)" % (tuple(hall.shape), tuple(dhall.shape)))
+        if gs is None or gs.numel() != 1 or gs.dtype != torch.float32:
+            raise ValueError("pixel_loss: gradient mode needs gs, a one-element float32 device tensor")
+    if base_total is not None and (base_total.numel() != 1 or base_total.dtype != torch.float32):
+        raise ValueError("pixel_loss: base_total must be a one-element float32 device tensor")
+    if out is None:
+        out = torch.empty((3,), dtype=torch.float32, device=hall.device)
+    elif out.numel() < 3 or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("pixel_loss: out must be a contiguous float32 tensor of at least 3 elements")
+    part = torch.empty((_PIXEL_PART,), dtype=torch.float32, device=hall.device)
+    check(_abi.load().hd_pixel_loss(ptr(hall), ptr(rgb), ptr(ir), N, 3, H, W, ir.shape[1], float(w_rgb), float(w_ir), k,
+                                    ptr(base_total), ptr(gs), ptr(dhall), ptr(part), ptr(out), _stream()), "hd_pixel_loss")
+    return out if base_total is not None else out[:2]

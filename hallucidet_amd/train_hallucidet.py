@@ -13,6 +13,7 @@ import torch.nn as nn
 from . import ops
 from .config import Config
 from .distributed import GradientAverager, broadcast_parameters, exchange_and_step
+from .losses.losses import PixelTerms, Reconstruction
 from .models.detector import Detector
 from .models.encoder_decoder import EncoderDecoder
 from .optim import LossScaler
@@ -59,9 +60,10 @@ class EncoderDecoderLit(nn.Module):
         self.scheduler_on = scheduler_on
         self.detector_name = detector_name
         self.dev = torch.device(device)
-        if loss_pixel is not None or loss_perceptual is not None:
-            raise NotImplementedError("pixel / LPIPS losses have weight 0.0 and selectors returning None in every BASELINE "
-                                      "config (SURVEY #17); their four keys are reported as 0.0")
+        # src/losses/losses.py through train_hallucidet.py:115-116: 'mse' / 'l1' -> the HIP pixel loss (hd_pixel_loss), anything else
+        # None; LPIPS raises (the `lpips` package and its weights are not available), the other perceptual names select nothing
+        self.loss_pixel = Reconstruction.select_loss_pixel(loss_pixel=loss_pixel)
+        self.loss_perceptual = Reconstruction.select_loss_perceptual(loss_perceptual=loss_perceptual)
         self.encoder_decoder = EncoderDecoder(name=self.model_name, encoder_depth=5, encoder_weights=None,
                                               decoder_attention_type=None, in_channels=self.in_channels,
                                               output_channels=self.output_channels,
@@ -114,14 +116,21 @@ class EncoderDecoderLit(nn.Module):
         graph = self._detector_graph() if (step == 'train' and not train_det and imgs_hallucinated.requires_grad) else None
         if graph is not None:
             # the detector half of the step (three passes, losses, the backward pass down to the hallucinated image, the deferred
-            # post-processing) as ONE hipGraph replay (det_graph.py); the U-Net's backward continues from the image gradient
+            # post-processing) as ONE hipGraph replay (det_graph.py); the U-Net's backward continues from the image gradient.  With a
+            # pixel loss the graph also holds its gradient-mode launch: `loss_det_total` is then the whole total
             losses_det, loss_det_total, (detections_hall, detections_rgb, detections_ir) = graph.step(
                 imgs_hallucinated, imgs_rgb, imgs_ir_three_channel, targets_rgb, targets_ir)
         else:
             losses_det, loss_det_total, (detections_hall, detections_rgb, detections_ir) = self._detector_section(
                 imgs_hallucinated, imgs_rgb, imgs_ir_three_channel, targets_rgb, targets_ir, step, train_det)
         total_loss = loss_det_total
-        for extra in (loss_pixel_rgb, loss_perceptual_rgb, loss_pixel_ir, loss_perceptual_ir):
+        if self.loss_pixel is not None:
+            if 'pixel_rgb' in losses_det:           # computed inside the detector graph (not after a failed capture)
+                loss_det_total = losses_det.pop('det_total')
+                loss_pixel_rgb, loss_pixel_ir = losses_det.pop('pixel_rgb'), losses_det.pop('pixel_ir')
+            else:
+                loss_pixel_rgb, loss_pixel_ir, total_loss = self._pixel_terms(imgs_hallucinated, loss_det_total, imgs_rgb, imgs_ir_three_channel)
+        for extra in (loss_perceptual_rgb, loss_perceptual_ir):
             if torch.is_tensor(extra) or extra != 0.0:
                 total_loss = total_loss + extra
 
@@ -183,6 +192,27 @@ class EncoderDecoderLit(nn.Module):
             if not any(k == kk for kk, _ in keys):
                 losses_det[k] = 0.0
         return losses_det, total, (detections_hall, detections_rgb, detections_ir)
+
+    def pixel_setup(self):
+        """-> (kind, w_rgb, w_ir) of the pixel loss, weights read from Config at call time like the detector weights; None when off."""
+        if self.loss_pixel is None:
+            return None
+        w = Config.Losses.hparams_losses_weights
+        return self.loss_pixel.kind, float(w['pixel_rgb']), float(w['pixel_ir'])
+
+    @staticmethod
+    def _pixel_ir_planes(imgs_ir_three_channel):
+        """The IR batch as hd_pixel_loss reads it: the one plane under a stride-0 three-channel view, else the batch itself."""
+        ir = imgs_ir_three_channel
+        if ir.dim() == 4 and ir.shape[1] > 1 and ir.stride(1) == 0:
+            ir = ir[:, :1]
+        return ir.contiguous()
+
+    def _pixel_terms(self, imgs_hallucinated, loss_det_total, imgs_rgb, imgs_ir_three_channel):
+        """train_hallucidet.py:173,175,209: (w_rgb * pixel(rgb, hall), w_ir * pixel(ir3, hall), det_total + both) as one autograd node."""
+        kind, w_rgb, w_ir = self.pixel_setup()
+        return PixelTerms.apply(imgs_hallucinated, loss_det_total.reshape(()).float(), imgs_rgb.contiguous(),
+                                self._pixel_ir_planes(imgs_ir_three_channel), kind, w_rgb, w_ir)
 
     def _loss_keys(self):
         frcnn, fcos_ = 'fasterrcnn' in self.detector_name, 'fcos' in self.detector_name

@@ -453,6 +453,17 @@ int hd_fastrcnn_loss_masked(const float* logits, const float* box_regression, co
 int hd_fastrcnn_loss_masked_bwd(const float* logits, const float* box_regression, const int64_t* labels, const float* reg_t, int R, int K,
                                 float beta, const int64_t* n_valid_dev, const float* g_cls, const float* g_box, float* d_logits,
                                 float* d_box_regression, void* stream);
+/* Pixel reconstruction losses (reference src/losses/losses.py: MSELoss / L1Loss; train_hallucidet.py:173-176,209), both terms in one
+ * streaming pass.  hall, rgb [N][C=3][H][W] fp32; ir [N][ir_channels][H][W] fp32, ir_channels 1 (one plane broadcast over the three
+ * channels) or 3; kind 0 = mse, 1 = l1.  With v(d) = d*d | |d| and n = N*3*H*W (also for a one-plane ir):
+ *   out[0] = w_rgb * sum v(hall - rgb) / n,  out[1] = w_ir * sum v(hall - ir) / n,
+ *   out[2] = (base_total[0] + out[0]) + out[1]         when base_total (a device scalar) is given.
+ * Gradient mode (dhall != NULL, same layout as hall): dhall[i] += gs[0] * (w_rgb * g(hall - rgb) + w_ir * g(hall - ir)) with
+ * g(d) = 2d/n | sign(d)/n, sign(0) = 0; gs = the device seed (loss scale).  The values are the same bits in both modes.
+ * Deterministic (fixed block partials, fixed-order final sum); no host synchronisation.  part_ws: 2048 floats.
+ * Null hall / rgb / ir / part_ws / out, C != 3, ir_channels not in {1, 3}, kind not in {0, 1}, or dhall without gs -> HD_E_ARG. */
+int hd_pixel_loss(const float* hall, const float* rgb, const float* ir, int N, int C, int H, int W, int ir_channels, float w_rgb,
+                  float w_ir, int kind, const float* base_total, const float* gs, float* dhall, float* part_ws, float* out, void* stream);
 /* BalancedPositiveNegativeSampler [EXT] for N images (reached from src/utils/eval_forward_fasterrcnn.py:90,127): labels [N][A]
  * i64 (>= 1 positive, 0 negative, < 0 ignored), keys [N][A] i32 >= 0 = one random key per candidate.  Per image
  * num_pos = min(#pos, cap_pos), num_neg = min(#neg, batch_size - num_pos); pos_sel / neg_sel [N][A] u8 mark the num_pos /
