@@ -116,6 +116,9 @@ class Config:
         p.add_argument("--pixel", type=str, default=None)
         p.add_argument("--weight-pixel-rgb", type=float, default=0.0)
         p.add_argument("--weight-pixel-ir", type=float, default=0.0)
+        # where validation / test compute COCO mAP: 'cpu' = the host evaluator, 'cuda' = the HIP evaluator (same numbers; with several
+        # ranks it reports the mAP of the whole split instead of the mean of the per-rank values)
+        p.add_argument("--map-device", type=str, default="cpu", choices=["cpu", "cuda"])
         p.add_argument("--perceptual", type=str, default=None)
         p.add_argument("--weight-perceptual-rgb", type=float, default=0.0)
         p.add_argument("--weight-perceptual-ir", type=float, default=0.0)

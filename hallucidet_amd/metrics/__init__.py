@@ -1,1 +1,2 @@
 from .metrics import Detection, MeanAveragePrecision, MAP  # noqa: F401
+from .device import DeviceMeanAveragePrecision, GlobalResult  # noqa: F401

@@ -48,7 +48,16 @@ class MeanAveragePrecision:
         self.reset()
 
     def to(self, device):
-        return self
+        """A CPU device keeps this host evaluator; a GPU device returns the device evaluator (metrics/device.py) with the same options
+        and the images seen so far."""
+        if torch.device(device).type == "cpu":
+            return self
+        from .device import DeviceMeanAveragePrecision
+        d = DeviceMeanAveragePrecision(class_metrics=self.class_metrics, device=device)
+        if self._gts:
+            d.update([{k: torch.from_numpy(v) for k, v in p.items()} for p in self._dets],
+                     [{k: torch.from_numpy(v) for k, v in t.items()} for t in self._gts])
+        return d
 
     def reset(self):
         self._dets: List[Dict[str, np.ndarray]] = []

@@ -1813,6 +1813,16 @@ class LazyDetections(list):
                 self._pad = tuple(thunk())
         return self
 
+    def padded(self):
+        """The whole batch as padded device tensors, without the per-image slicing (no host sync): (boxes [n,D,4] after box_fn,
+        scores [n,D], labels [n,D], counts [n]); image i holds the first counts[i] rows.  Flushes first; None once materialised."""
+        if self._thunk is not None or self._parent is not None:
+            self.flush()
+        if self._pad is None:
+            return None
+        b, s, l, counts, fn = self._pad
+        return (fn(b) if fn is not None else b), s, l, counts
+
     def _materialize(self):
         if self._thunk is not None or self._parent is not None:
             self.flush()

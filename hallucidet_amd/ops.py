@@ -1124,3 +1124,69 @@ def pixel_loss(hall, rgb, ir, kind, w_rgb, w_ir, *, base_total=None, gs=None, dh
     check(_abi.load().hd_pixel_loss(ptr(hall), ptr(rgb), ptr(ir), N, 3, H, W, ir.shape[1], float(w_rgb), float(w_ir), k,
                                     ptr(base_total), ptr(gs), ptr(dhall), ptr(part), ptr(out), _stream()), "hd_pixel_loss")
     return out if base_total is not None else out[:2]
+
+
+# COCO mAP evaluation grid of hd_map_match / hd_map_accumulate (include/hallucidet_hip.h)
+MAP_NUM_IOU, MAP_NUM_AREA, MAP_NUM_MAXDET, MAP_NUM_REC = 10, 4, 3, 101
+MAP_MAX_DET, MAP_DET_CAP, MAP_GT_CAP = 100, 1024, 512
+
+
+def _need(t, dtype, shape, name, what):
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError("%s: %s must be a contiguous %s tensor of shape %s (got %s %s)" % (what, name, dtype, tuple(shape), t.dtype,
+                                                                                        tuple(t.shape)))
+
+
+def map_match(det_boxes, det_scores, det_labels, det_count, gt_boxes, gt_labels, gt_count, classes, iou_start, area_rng):
+    """hd_map_match: per (image, class) ranking and greedy matching.  det_boxes [N,P,4] f64, det_scores [N,P] f64, det_labels [N,P] i64,
+    det_count [N] i32; gt_boxes [N,Q,4] f64, gt_labels [N,Q] i64, gt_count [N] i32; classes [K] i64; iou_start [10] f64; area_rng
+    [4,2] f64, all on the GPU.  -> (flags [4, N*K*100] i32, score [N*K*100] f64, ndet [N*K] i32, npos [N*K, 4] i32, evald [N*K] i32,
+    status [3] i32), on the current stream, without a host sync; the caller reads `status` (cap overflows) before using the rest."""
+    _need_cuda(det_boxes, det_scores, det_labels, det_count, gt_boxes, gt_labels, gt_count, classes, iou_start, area_rng)
+    N, P = det_scores.shape
+    Q = gt_labels.shape[1]
+    K = classes.shape[0]
+    w = "map_match"
+    _need(det_boxes, torch.float64, (N, P, 4), "det_boxes", w)
+    _need(det_scores, torch.float64, (N, P), "det_scores", w)
+    _need(det_labels, torch.int64, (N, P), "det_labels", w)
+    _need(det_count, torch.int32, (N,), "det_count", w)
+    _need(gt_boxes, torch.float64, (N, Q, 4), "gt_boxes", w)
+    _need(gt_labels, torch.int64, (N, Q), "gt_labels", w)
+    _need(gt_count, torch.int32, (N,), "gt_count", w)
+    _need(classes, torch.int64, (K,), "classes", w)
+    _need(iou_start, torch.float64, (MAP_NUM_IOU,), "iou_start", w)
+    _need(area_rng, torch.float64, (MAP_NUM_AREA, 2), "area_rng", w)
+    dev = det_scores.device
+    nk = N * K
+    flags = torch.empty((MAP_NUM_AREA, nk * MAP_MAX_DET), dtype=torch.int32, device=dev)
+    score = torch.empty((nk * MAP_MAX_DET,), dtype=torch.float64, device=dev)
+    ndet = torch.empty((nk,), dtype=torch.int32, device=dev)
+    npos = torch.empty((nk, MAP_NUM_AREA), dtype=torch.int32, device=dev)
+    evald = torch.empty((nk,), dtype=torch.int32, device=dev)
+    status = torch.zeros((3,), dtype=torch.int32, device=dev)
+    check(_abi.load().hd_map_match(ptr(det_boxes), ptr(det_scores), ptr(det_labels), ptr(det_count), N, P, ptr(gt_boxes), ptr(gt_labels),
+                                   ptr(gt_count), Q, ptr(classes), K, ptr(iou_start), ptr(area_rng), ptr(flags), ptr(score), ptr(ndet),
+                                   ptr(npos), ptr(evald), ptr(status), _stream()), "hd_map_match")
+    return flags, score, ndet, npos, evald, status
+
+
+def map_accumulate(order, class_off, flags, npig, n_eval, rec_thrs):
+    """hd_map_accumulate: order [L] i32 (entry ids grouped by class, each class in the global score order), class_off [K+1] i32,
+    flags [4, N*K*100] i32 (map_match), npig [K, 4] i32, n_eval [K] i32, rec_thrs [101] f64.
+    -> (precision [10, 101, K, 4, 3], recall [10, K, 4, 3]) f64 on the GPU, the host evaluator's arrays."""
+    _need_cuda(order, class_off, flags, npig, n_eval, rec_thrs)
+    K = n_eval.shape[0]
+    w = "map_accumulate"
+    _need(order, torch.int32, (order.shape[0],), "order", w)
+    _need(class_off, torch.int32, (K + 1,), "class_off", w)
+    _need(flags, torch.int32, (MAP_NUM_AREA, flags.shape[1]), "flags", w)
+    _need(npig, torch.int32, (K, MAP_NUM_AREA), "npig", w)
+    _need(n_eval, torch.int32, (K,), "n_eval", w)
+    _need(rec_thrs, torch.float64, (MAP_NUM_REC,), "rec_thrs", w)
+    dev = n_eval.device
+    precision = torch.empty((MAP_NUM_IOU, MAP_NUM_REC, K, MAP_NUM_AREA, MAP_NUM_MAXDET), dtype=torch.float64, device=dev)
+    recall = torch.empty((MAP_NUM_IOU, K, MAP_NUM_AREA, MAP_NUM_MAXDET), dtype=torch.float64, device=dev)
+    check(_abi.load().hd_map_accumulate(ptr(order), ptr(class_off), ptr(flags), flags.shape[1], ptr(npig), ptr(n_eval), K, ptr(rec_thrs),
+                                        ptr(precision), ptr(recall), _stream()), "hd_map_accumulate")
+    return precision, recall

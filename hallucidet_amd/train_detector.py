@@ -24,12 +24,13 @@ from .utils.utils import Utils
 
 class DetectorLit:
     def __init__(self, batch_size=4, wandb_logger=None, lr=0.0001, detector_name='fasterrcnn', pretrained=True, optimizer_name='adam',
-                 modality=None, directly_coco=False, detector=None, device='cuda', loss_scale=1024.0, precision=16):
+                 modality=None, directly_coco=False, detector=None, device='cuda', loss_scale=1024.0, precision=16, map_device='cpu'):
         if not any(k in detector_name for k in ('fasterrcnn', 'retinanet', 'fcos')):
             raise ValueError("unknown detector %r (fasterrcnn / retinanet / fcos)" % (detector_name,))
         self.wandb_logger, self.lr, self.batch_size = wandb_logger, lr, batch_size
         self.optimizer_name, self.detector_name, self.modality = optimizer_name, detector_name, modality
         self.dev = device
+        self.map_device = map_device          # 'cpu': host COCO mAP evaluator (default); 'cuda': the HIP one (metrics/device.py)
         self.detector = detector if detector is not None else Detector(name=detector_name, pretrained=pretrained,
                                                                        n_classes=getattr(getattr(Config, 'Dataset', None), 'n_classes', 2), size=Config.Detector.input_size,
                                                                        modality=modality, directly_coco=directly_coco).detector
@@ -135,12 +136,15 @@ class DetectorLit:
         from .metrics import Detection
         store = self.__dict__.setdefault("_map_metrics", {})
         if split not in store:
-            store[split] = Detection(class_metrics=True).map      # train_detector.py:115-116
+            dev = self.dev if (torch.device(self.map_device).type == "cuda" and torch.device(self.dev).type == "cuda") else self.map_device
+            store[split] = Detection(device=dev, class_metrics=True).map      # train_detector.py:115-116
         return store[split]
 
     def _epoch_end(self, split):
+        from .metrics.device import carry_global
         m = self._metric(split)
-        out = Utils.filter_dictionary(m.compute(), {'map_50', 'map_75', 'map', 'map_per_class'})
+        r = m.compute()
+        out = carry_global(r, Utils.filter_dictionary(r, {'map_50', 'map_75', 'map', 'map_per_class'}))
         m.reset()
         return out
 

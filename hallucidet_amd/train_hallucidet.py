@@ -50,7 +50,7 @@ class _WeightedLosses(torch.autograd.Function):
 class EncoderDecoderLit(nn.Module):
     def __init__(self, batch_size=4, wandb_logger=None, model_name='resnet34', in_channels=3, output_channels=3, lr=0.0001,
                  loss_pixel=None, loss_perceptual=None, detector_name='fasterrcnn', train_det=False, fuse_data='none',
-                 scheduler_on=False, detector=None, precision=16, device='cuda', use_graphs=True):
+                 scheduler_on=False, detector=None, precision=16, device='cuda', use_graphs=True, map_device='cpu'):
         super().__init__()
         self.model_name, self.wandb_logger = model_name, wandb_logger
         self.in_channels, self.output_channels = in_channels, output_channels
@@ -60,6 +60,8 @@ class EncoderDecoderLit(nn.Module):
         self.scheduler_on = scheduler_on
         self.detector_name = detector_name
         self.dev = torch.device(device)
+        # where the COCO mAP accumulators live: 'cpu' = the host evaluator (default), 'cuda' = the HIP one (metrics/device.py)
+        self.map_device = map_device
         # src/losses/losses.py through train_hallucidet.py:115-116: 'mse' / 'l1' -> the HIP pixel loss (hd_pixel_loss), anything else
         # None; LPIPS raises (the `lpips` package and its weights are not available), the other perceptual names select nothing
         self.loss_pixel = Reconstruction.select_loss_pixel(loss_pixel=loss_pixel)
@@ -251,11 +253,12 @@ class EncoderDecoderLit(nn.Module):
         return save_lightning_checkpoint(path, {"encoder_decoder": self.encoder_decoder, "detector": self.detector}, epoch, global_step)
 
     def _metrics(self, split):
-        """train_hallucidet.py:121-131: one COCO-style mAP accumulator per (split, stream)."""
+        """train_hallucidet.py:121-131: one COCO-style mAP accumulator per (split, stream), on `map_device`."""
         from .metrics import Detection
         store = self.__dict__.setdefault("_map_metrics", {})
         if split not in store:
-            store[split] = {k: Detection().map for k in ("hall", "rgb", "ir")}
+            dev = self.dev if (torch.device(self.map_device).type == "cuda" and self.dev.type == "cuda") else self.map_device
+            store[split] = {k: Detection(device=dev).map for k in ("hall", "rgb", "ir")}
         return store[split]
 
     def _eval_step(self, batch, batch_idx, split):
@@ -275,8 +278,12 @@ class EncoderDecoderLit(nn.Module):
         return self._eval_step(test_batch, batch_idx, 'test')
 
     def _epoch_end(self, split):
+        from .metrics.device import carry_global
         m = self._metrics(split)
-        out = {"map_" + k: Utils.filter_dictionary(m[k].compute(), {'map_50', 'map_75', 'map'}) for k in ("rgb", "hall", "ir")}
+        out = {}
+        for k in ("rgb", "hall", "ir"):
+            r = m[k].compute()
+            out["map_" + k] = carry_global(r, Utils.filter_dictionary(r, {'map_50', 'map_75', 'map'}))
         for v in m.values():
             v.reset()
         return out

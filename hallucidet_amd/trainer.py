@@ -73,12 +73,25 @@ class Trainer:
         return float(t[0]) / max(float(t[1]), 1.0)
 
     @staticmethod
-    def _nanmean_over_ranks(metrics):
+    def _global_keys(metrics):
+        """Flat keys (as _flat names them) of the results that already cover every rank (metrics.device.GlobalResult)."""
+        out = set()
+        for k, v in metrics.items():
+            if isinstance(v, dict) and getattr(v, "is_global", False):
+                out |= {"%s/%s" % (k, k2) for k2, v2 in v.items() if torch.is_tensor(v2) and v2.numel() == 1}
+            elif getattr(metrics, "is_global", False) and torch.is_tensor(v) and v.numel() == 1:
+                out.add(k)
+        return out
+
+    @staticmethod
+    def _nanmean_over_ranks(metrics, passthrough=()):
         """All monitored scalars in ONE unconditional all-reduce: per key a (sum, count) pair, NaN / 'no data' (-1 from the mAP
         accumulators) entries contribute (0, 0).  Every rank issues the same collective whatever its local values are -- a
-        per-key reduce guarded by a local NaN test would pair up differently on ranks whose values differ."""
+        per-key reduce guarded by a local NaN test would pair up differently on ranks whose values differ.  Keys in `passthrough`
+        (global results, identical on every rank; every rank names the same ones) are returned as they are."""
         from .distributed import is_dist
-        keys = sorted(metrics)
+        out = {k: float(metrics[k]) for k in passthrough if k in metrics}
+        keys = sorted(k for k in metrics if k not in out)
         pairs = []
         for k in keys:
             v = metrics[k]
@@ -91,7 +104,6 @@ class Trainer:
             t = torch.tensor(pairs, dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
             dist.all_reduce(t)
             pairs = t.tolist()
-        out = {}
         for i, k in enumerate(keys):
             s, c = pairs[2 * i], pairs[2 * i + 1]
             if c > 0:
@@ -117,11 +129,12 @@ class Trainer:
                 r = model.validation_step(batch, i)
                 tot += float(r[0] if isinstance(r, tuple) else r)
                 n += 1
-            m = self._flat(model.on_validation_epoch_end())
+            out = model.on_validation_epoch_end()
+            m, glob = self._flat(out), self._global_keys(out)
             self._flush_deferred_checks(model)
         finally:
             self._restore(state)
-        m.update(self._nanmean_over_ranks(dict(m, val_loss=(tot, n))))
+        m.update(self._nanmean_over_ranks(dict(m, val_loss=(tot, n)), passthrough=glob))
         # Lightning logs `val_map` = the hallucinated stream's mAP (train_hallucidet.py:357) / the detector's mAP
         m["val_map"] = m.get("map_hall/map", m.get("map", float("nan")))
         return m

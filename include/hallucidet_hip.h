@@ -464,6 +464,34 @@ int hd_fastrcnn_loss_masked_bwd(const float* logits, const float* box_regression
  * Null hall / rgb / ir / part_ws / out, C != 3, ir_channels not in {1, 3}, kind not in {0, 1}, or dhall without gs -> HD_E_ARG. */
 int hd_pixel_loss(const float* hall, const float* rgb, const float* ir, int N, int C, int H, int W, int ir_channels, float w_rgb,
                   float w_ir, int kind, const float* base_total, const float* gs, float* dhall, float* part_ws, float* out, void* stream);
+/* COCO mAP on the device (hallucidet_amd/metrics/metrics.py `_evaluate_img` / `_accumulate`, restated bit for bit; csrc/coco_map.hip).
+ * Fixed evaluation grid: 10 IoU thresholds, 4 area ranges (all, small, medium, large), max-dets 1 / 10 / 100, 101 recall thresholds. */
+#define HD_MAP_NUM_IOU 10
+#define HD_MAP_NUM_AREA 4
+#define HD_MAP_NUM_MAXDET 3
+#define HD_MAP_NUM_REC 101
+#define HD_MAP_MAX_DET 100     /* detections kept per (image, class): the largest max-dets */
+#define HD_MAP_DET_CAP 1024    /* most detections of one class in one image */
+#define HD_MAP_GT_CAP 512      /* most ground truths of one class in one image */
+/* Matching, one wave per (image n, class k), item = n * K + k.  Detections padded per image: det_boxes [N][P][4] f64 (xyxy),
+ * det_scores [N][P] f64, det_labels [N][P] i64, det_count [N] i32 (the first det_count[n] entries are real); ground truths likewise
+ * gt_boxes [N][Q][4], gt_labels [N][Q], gt_count [N].  classes [K] i64; iou_start [10] = min(t, 1 - 1e-10) per IoU threshold;
+ * area_rng [4][2] f64.  Outputs, for rank r < ndet[item] (<= 100) of the class-k detections ordered by descending score (ties: lower
+ * index first): score[item*100 + r]; flags[a][item*100 + r] i32, bit t = matched at threshold t, bit 10 + t = ignored at threshold t;
+ * npos[item][4] = non-ignored ground truths per area; evald[item] = 1 when the image has a detection or a ground truth of class k.
+ * status [3] i32, zeroed by the caller: [0] = largest class detection count above HD_MAP_DET_CAP, [1] = largest class ground-truth
+ * count above HD_MAP_GT_CAP (such items are left unevaluated), [2] = 1 if a count lay outside [0, P] / [0, Q].  No host sync. */
+int hd_map_match(const double* det_boxes, const double* det_scores, const int64_t* det_labels, const int32_t* det_count, int N, int P,
+                 const double* gt_boxes, const int64_t* gt_labels, const int32_t* gt_count, int Q, const int64_t* classes, int K,
+                 const double* iou_start, const double* area_rng, int32_t* flags, double* score, int32_t* ndet, int32_t* npos,
+                 int32_t* evald, int32_t* status, void* stream);
+/* Accumulation, one block per (threshold t, class k, area a, max-dets m).  order: hd_map_match entry ids (item*100 + r), grouped by
+ * class (class k = order[class_off[k] .. class_off[k+1])) and within a class sorted by descending score, then entry id; flags /
+ * nk100 = hd_map_match's flags and its per-area stride N*K*100; npig [K][4] = npos summed over images; n_eval [K] = evaluated images;
+ * rec_thrs [101] f64.  Writes precision [10][101][K][4][3] and recall [10][K][4][3] f64 with the host's conventions (-1 where no
+ * image was evaluated or npig == 0, recall 0 for an empty curve).  Deterministic: integer scans and integer max only. */
+int hd_map_accumulate(const int32_t* order, const int32_t* class_off, const int32_t* flags, int64_t nk100, const int32_t* npig,
+                      const int32_t* n_eval, int K, const double* rec_thrs, double* precision, double* recall, void* stream);
 /* BalancedPositiveNegativeSampler [EXT] for N images (reached from src/utils/eval_forward_fasterrcnn.py:90,127): labels [N][A]
  * i64 (>= 1 positive, 0 negative, < 0 ignored), keys [N][A] i32 >= 0 = one random key per candidate.  Per image
  * num_pos = min(#pos, cap_pos), num_neg = min(#neg, batch_size - num_pos); pos_sel / neg_sel [N][A] u8 mark the num_pos /
