@@ -15,6 +15,9 @@ from train_hallucidet import print_ap50
 def main(argv=None):
     Config.set_environment()
     args = Config.argument_parser(argv)
+    if args.augment != "none":
+        raise SystemExit("eval_hallucidet.py: --augment %s is an option of train_detector.py (evaluation reads the raw images); use "
+                         "--augment none" % args.augment)
     torch.manual_seed(args.seed)
     dataset = args.dataset or "llvip"
     Config.set_detector(args.detector, train_det=False, pretrained=args.directly_coco, dataset=dataset)

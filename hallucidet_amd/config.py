@@ -119,6 +119,9 @@ class Config:
         # where validation / test compute COCO mAP: 'cpu' = the host evaluator, 'cuda' = the HIP evaluator (same numbers; with several
         # ranks it reports the mAP of the whole split instead of the mean of the per-rank values)
         p.add_argument("--map-device", type=str, default="cpu", choices=["cpu", "cuda"])
+        # train_detector.py: 'reference' = the reference's photometric augmentation of the training split (train_detector.py:401-410),
+        # applied to the uint8 batch on the GPU (dataloader/augment.py)
+        p.add_argument("--augment", type=str, default="none", choices=["none", "reference"])
         p.add_argument("--perceptual", type=str, default=None)
         p.add_argument("--weight-perceptual-rgb", type=float, default=0.0)
         p.add_argument("--weight-perceptual-ir", type=float, default=0.0)

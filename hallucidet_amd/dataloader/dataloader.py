@@ -279,7 +279,11 @@ class DevicePrefetcher:
     of two reusable pinned buffers per image group, copied on a side HIP stream and divided by 255 on the GPU; the per-image target tensors of one key travel as ONE concatenated pinned copy and are split into views on
     the device (a pageable .to(device) per tensor is a blocking copy each: 64 of them per LLVIP batch)."""
 
-    def __init__(self, loader, device="cuda"):
+    def __init__(self, loader, device="cuda", augment=None):
+        """augment: a `ReferenceAugmentation` (dataloader/augment.py) or None.  When given, single-modal batches are augmented as
+        uint8, before the division by 255: the per-image parameter rows are drawn for (epoch, batch index), travel as one pinned copy
+        and `ops.augment_u8` runs on the staging stream (`apply_host` on a CPU device)."""
+        self.augment, self._batch, self._aug_ws = augment, -1, None
         self.loader, self.device = loader, torch.device(device)
         self.cuda = self.device.type == "cuda"
         if self.cuda and self.device.index is None:          # the staging thread needs the concrete device
@@ -315,12 +319,27 @@ class DevicePrefetcher:
         return dev
 
     def _stage(self, batch):
-        def imgs(g, seq):
+        def imgs(g, seq, augment=None):
             seq = list(seq)
             if seq and seq[0].is_cuda:
                 u8 = torch.stack(seq)
             else:
                 u8 = self._upload(("img", g), seq, True)
+            if augment is not None:
+                if u8.dtype != torch.uint8:
+                    raise TypeError("DevicePrefetcher: the augmentation takes uint8 images (got %s)" % u8.dtype)
+                rows = augment.params_for(u8.shape[0], self._batch)
+                if u8.is_cuda:
+                    from .. import ops
+                    need = ops.augment_ws_bytes(u8.shape)
+                    if self._aug_ws is None or self._aug_ws.numel() < need:       # one workspace: every call runs on the staging stream
+                        self._aug_ws = torch.empty((need,), dtype=torch.uint8, device=u8.device)
+                    u8 = ops.augment_u8(u8, self._upload(("aug", g), [rows], False), ws=self._aug_ws)
+                    # a tensor divisor: the IEEE division the host path computes (a Python-scalar divisor is a multiplication by
+                    # fp32(1/255) on the GPU, up to one ulp away), so both devices yield the same floats
+                    return u8.float().div_(torch.full((), 255.0, device=u8.device))
+                from .augment import apply_host
+                u8 = apply_host(u8, rows)
             return u8.float().div_(255.0) if u8.dtype == torch.uint8 else u8.float()
 
         def tgts(g, seq):
@@ -339,11 +358,15 @@ class DevicePrefetcher:
                         o[k] = v.to(self.device, non_blocking=True)
             return out
         if len(batch) == 4:
+            if self.augment is not None:
+                raise ValueError("DevicePrefetcher: the augmentation is defined for single-modal (image, target) batches only; the "
+                                 "reference's HalluciDet training has none")
             return imgs(0, batch[0]), tgts(0, batch[1]), imgs(1, batch[2]), tgts(1, batch[3])
-        return imgs(0, batch[0]), tgts(0, batch[1])
+        return imgs(0, batch[0], self.augment), tgts(0, batch[1])
 
     def __iter__(self):
         it = iter(self.loader)
+        self._batch = -1
 
         def fetch():
             try:
@@ -351,6 +374,7 @@ class DevicePrefetcher:
             except StopIteration:
                 return None
             self._turn += 1
+            self._batch += 1
             if self.stream is None:
                 return self._stage(b)
             torch.cuda.set_device(self.device)

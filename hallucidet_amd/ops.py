@@ -1126,6 +1126,47 @@ def pixel_loss(hall, rgb, ir, kind, w_rgb, w_ir, *, base_total=None, gs=None, dh
     return out if base_total is not None else out[:2]
 
 
+AUG_ROW = 12                    # floats per image in hd_augment_u8's parameter record (HD_AUG_ROW)
+AUG_MAX_PIXELS = 16843009       # largest H*W of hd_augment_u8: its image sums are 32-bit integers (HD_AUG_MAX_PIXELS)
+
+
+def augment_ws_bytes(shape):
+    """bytes of workspace hd_augment_u8 needs for a batch of `shape` = (N, C, H, W)"""
+    n = int(_abi.load().hd_augment_u8_ws_bytes(*[int(v) for v in shape]))
+    if n < 0:
+        raise ValueError("augment_u8: need 1 <= N <= 65535, C in (1, 3), H, W >= 3 and H*W <= %d (got %s)" % (AUG_MAX_PIXELS, tuple(shape)))
+    return n
+
+
+def augment_u8(u8, params, out=None, ws=None):
+    """hd_augment_u8: the reference's photometric detector-training augmentation (dataloader/augment.py) on a contiguous uint8 batch
+    [N, 1 or 3, H, W] on the GPU, bit for bit Pillow's result.  `params`: float32 [N, AUG_ROW] on the same device, one row per image
+    (layout: include/hallucidet_hip.h).  One memset + four launches on the current stream whatever N and the rows say; no host sync.
+    `ws`: a uint8 device tensor of at least `augment_ws_bytes(u8.shape)` bytes that a caller keeps across calls ON ONE STREAM (the
+    calls then run in order); allocated per call when None."""
+    _need_cuda(u8, params, out, ws)
+    if u8.dim() != 4 or u8.dtype != torch.uint8 or not u8.is_contiguous():
+        raise ValueError("augment_u8: images must be a contiguous uint8 [N, C, H, W] tensor (got %s %s)" % (u8.dtype, tuple(u8.shape)))
+    N, Cc, H, W = u8.shape
+    if Cc not in (1, 3) or H < 3 or W < 3 or N < 1 or N > 65535 or H * W > AUG_MAX_PIXELS:
+        raise ValueError("augment_u8: need 1 <= N <= 65535, C in (1, 3), H, W >= 3 and H*W <= %d (got %s)" % (AUG_MAX_PIXELS, tuple(u8.shape)))
+    if params.dtype != torch.float32 or tuple(params.shape) != (N, AUG_ROW) or not params.is_contiguous():
+        raise ValueError("augment_u8: params must be a contiguous float32 [%d, %d] tensor (got %s %s)" % (N, AUG_ROW, params.dtype,
+                                                                                                         tuple(params.shape)))
+    if out is None:
+        out = torch.empty_like(u8)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != tuple(u8.shape) or not out.is_contiguous():
+        raise ValueError("augment_u8: out must be a contiguous uint8 tensor of shape %s" % (tuple(u8.shape),))
+    lib = _abi.load()
+    need = augment_ws_bytes(u8.shape)
+    if ws is None:
+        ws = torch.empty((need,), dtype=torch.uint8, device=u8.device)
+    elif ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous():
+        raise ValueError("augment_u8: ws must be a contiguous uint8 tensor of at least %d bytes" % need)
+    check(lib.hd_augment_u8(ptr(u8), ptr(params), N, Cc, H, W, ptr(out), ptr(ws), _stream()), "hd_augment_u8")
+    return out
+
+
 # COCO mAP evaluation grid of hd_map_match / hd_map_accumulate (include/hallucidet_hip.h)
 MAP_NUM_IOU, MAP_NUM_AREA, MAP_NUM_MAXDET, MAP_NUM_REC = 10, 4, 3, 101
 MAP_MAX_DET, MAP_DET_CAP, MAP_GT_CAP = 100, 1024, 512

@@ -464,6 +464,22 @@ int hd_fastrcnn_loss_masked_bwd(const float* logits, const float* box_regression
  * Null hall / rgb / ir / part_ws / out, C != 3, ir_channels not in {1, 3}, kind not in {0, 1}, or dhall without gs -> HD_E_ARG. */
 int hd_pixel_loss(const float* hall, const float* rgb, const float* ir, int N, int C, int H, int W, int ir_channels, float w_rgb,
                   float w_ir, int kind, const float* base_total, const float* gs, float* dhall, float* part_ws, float* out, void* stream);
+/* Photometric training augmentation of the reference's detector recipe (train_detector.py:401-410: ColorJitter, RandomInvert,
+ * RandomAdjustSharpness, RandomEqualize) on a planar uint8 batch, bit for bit what Pillow computes (csrc/augment.hip).
+ * x, out [N][C][H][W] uint8, C = 3 (RGB) or 1 (PIL mode L), H, W >= 3, H*W <= HD_AUG_MAX_PIXELS (the image sums are 32-bit integers),
+ * N <= 65535.  params [N][HD_AUG_ROW] fp32 on the device, one row per image:
+ *   [0..3] the jitter operations in the order they run: 0 brightness, 1 contrast, 2 saturation, 3 hue, -1 none;
+ *   [4] brightness, [5] contrast, [6] saturation factor; [7] hue factor h (the H channel moves by trunc(h * 255), wrapping);
+ *   [8] invert, [9] sharpness, [10] equalize flags (non-zero = on), run in this order after the jitter; [11] sharpness factor.
+ * Saturation and hue are the identity for C = 1.  ws: hd_augment_u8_ws_bytes(N, C, H, W) bytes of device memory, 16-byte aligned,
+ * contents irrelevant.  One memset and four launches whatever N and the rows say; no host synchronisation; the result is the same
+ * bits from run to run (integer accumulators only).  With x / out 16-byte aligned, the three pointwise passes move 16 bytes per lane
+ * when H*W % 16 == 0 and the sharpness pass when W % 16 == 0; any other shape (127 x 161) is correct but takes the slow path of one
+ * byte per lane. */
+#define HD_AUG_ROW 12
+#define HD_AUG_MAX_PIXELS 16843009 /* 255 * H*W < 2^32 */
+int64_t hd_augment_u8_ws_bytes(int N, int C, int H, int W); /* < 0: bad shape (HD_E_ARG) */
+int hd_augment_u8(const uint8_t* x, const float* params, int N, int C, int H, int W, uint8_t* out, void* ws, void* stream);
 /* COCO mAP on the device (hallucidet_amd/metrics/metrics.py `_evaluate_img` / `_accumulate`, restated bit for bit; csrc/coco_map.hip).
  * Fixed evaluation grid: 10 IoU thresholds, 4 area ranges (all, small, medium, large), max-dets 1 / 10 / 100, 101 recall thresholds. */
 #define HD_MAP_NUM_IOU 10

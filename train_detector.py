@@ -35,8 +35,13 @@ def main(argv=None):
     model = DetectorLit.load_from_checkpoint(args.pre_train_path, **kw) if args.pre_train_path else DetectorLit(**kw)
     model.prepare()
     out_dir = os.path.join("lightning_logs", args.wandb_project, args.wandb_name, "_".join([dataset, args.modality, Config.Detector.name]))
+    augment = None
+    if args.augment == "reference":
+        from hallucidet_amd.dataloader.augment import ReferenceAugmentation
+        augment = ReferenceAugmentation(seed=args.seed, rank=rank)
     tr = Trainer(max_epochs=args.epochs, limit_train_batches=args.limit_train_batches, dirpath=out_dir if rank == 0 else None, monitor="val_map",
-                 mode="max", early_stopping=("val_map", "max", 5), device=dev, log=print if rank == 0 else (lambda *a: None))
+                 mode="max", early_stopping=("val_map", "max", 5), device=dev, log=print if rank == 0 else (lambda *a: None),
+                 train_augment=augment)
     tr.fit(model, dm)
     if rank == 0:
         print("test:", {k: (v.tolist() if torch.is_tensor(v) else v) for k, v in tr.test(model, dm).items()})

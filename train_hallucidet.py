@@ -25,6 +25,9 @@ def print_ap50(maps):
 def main(argv=None):
     Config.set_environment()
     args = Config.argument_parser(argv)
+    if args.augment != "none":
+        raise SystemExit("train_hallucidet.py: --augment %s is an option of train_detector.py (the reference's HalluciDet training has no "
+                         "augmentation); use --augment none" % args.augment)
     torch.manual_seed(args.seed)
     dataset = args.dataset or "llvip"
     Config.set_detector(args.detector, train_det=False, pretrained=args.directly_coco, dataset=dataset)
