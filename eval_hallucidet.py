@@ -26,7 +26,8 @@ def main(argv=None):
     dm = MultiModalDataModule(dataset, args.test, args.test, args.test, args.test, batch_size=args.batch, num_workers=args.num_workers,
                               ext=args.ext or ".jpg", seed=args.seed)
     kw = dict(batch_size=args.batch, model_name=args.decoder_backbone, detector_name=Config.Detector.name, precision=args.precision, device=dev,
-              loss_pixel=Config.Losses.pixel, loss_perceptual=Config.Losses.perceptual, map_device=args.map_device)
+              loss_pixel=Config.Losses.pixel, loss_perceptual=Config.Losses.perceptual, map_device=args.map_device,
+              ir_preprocess=args.ir_preprocess)
     model = EncoderDecoderLit.load_from_checkpoint(args.hallucidet_path, strict=False, **kw) if args.hallucidet_path else EncoderDecoderLit(**kw)
     if args.detector_path:
         from hallucidet_amd.checkpoint import load_detector
@@ -35,7 +36,7 @@ def main(argv=None):
     model.detector.to(dev)
     model.eval()            # Lightning's test loop: BatchNorm on the checkpoint's running statistics, detector in eval mode
     maps = Trainer(device=dev).test(model, dm)
-    print_ap50(maps)
+    print_ap50(maps, ir_preprocess=args.ir_preprocess)
     return maps
 
 

@@ -122,6 +122,11 @@ class Config:
         # train_detector.py: 'reference' = the reference's photometric augmentation of the training split (train_detector.py:401-410),
         # applied to the uint8 batch on the GPU (dataloader/augment.py)
         p.add_argument("--augment", type=str, default="none", choices=["none", "reference"])
+        # the image-space IR pre-processing baselines of the reference (models/cnnBasedThermalInfraredDA.py), on the GPU: in
+        # eval_hallucidet.py / train_hallucidet.py what the "RGB Detector on IR" pass reads in validation and test; in
+        # train_detector.py --modality ir what the detector is fine-tuned and evaluated on
+        from .models.cnnBasedThermalInfraredDA import IR_PREPROCESS_NAMES
+        p.add_argument("--ir-preprocess", type=str, default="none", choices=list(IR_PREPROCESS_NAMES))
         p.add_argument("--perceptual", type=str, default=None)
         p.add_argument("--weight-perceptual-rgb", type=float, default=0.0)
         p.add_argument("--weight-perceptual-ir", type=float, default=0.0)

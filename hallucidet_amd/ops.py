@@ -1167,6 +1167,70 @@ def augment_u8(u8, params, out=None, ws=None):
     return out
 
 
+IRP_INVERT, IRP_STRETCH, IRP_EQUALIZE, IRP_BLUR = 0, 1, 2, 3     # HD_IRP_* operation codes of hd_ir_preprocess
+IRP_MAX_STAGES = 4
+IRP_MAX_PIXELS = 1 << 24          # largest H*W of hd_ir_preprocess: its quantile ranks are formed in fp32 (HD_IRP_MAX_PIXELS)
+
+
+def irp_stage(op, channels=(0, 1, 2)):
+    """One stage entry of `ir_preprocess`: op | channel_mask << 8."""
+    mask = 0
+    for c in channels:
+        if c not in (0, 1, 2):
+            raise ValueError("ir_preprocess: channels are 0, 1, 2 (got %r)" % (c,))
+        mask |= 1 << c
+    return int(op) | mask << 8
+
+
+def _irp_shape_msg(shape, n_stage):
+    return ("ir_preprocess: need N >= 1, C in (1, 3), N*C <= 65535, H, W >= 2, H*W <= %d and 1..%d stages (got %s, %d stages)"
+            % (IRP_MAX_PIXELS, IRP_MAX_STAGES, tuple(shape), n_stage))
+
+
+def ir_preprocess_ws_bytes(shape, n_stage):
+    """bytes of workspace hd_ir_preprocess needs for a batch of `shape` = (N, C, H, W) and a list of `n_stage` stages"""
+    n = int(_abi.load().hd_ir_preprocess_ws_bytes(*([int(v) for v in shape] + [int(n_stage)])))
+    if n < 0:
+        raise ValueError(_irp_shape_msg(shape, n_stage))
+    return n
+
+
+def ir_preprocess(x, stages, out=None, q_out=None, ws=None):
+    """hd_ir_preprocess: the reference's image-space IR pre-processing baselines (models/cnnBasedThermalInfraredDA.py) on a contiguous
+    fp32 batch [N, 1 or 3, H, W] on the GPU.  `stages`: 1..4 ints `op | channel_mask << 8` (`irp_stage`), run in order, per image and
+    per channel; a channel outside a stage's mask passes through (semantics: include/hallucidet_hip.h).  `q_out`: optional fp32
+    [N, C, 2] receiving (q_min, q_max) of the last stretch stage.  A fixed launch list per stage list on the current stream, no host
+    sync.  `ws`: a uint8 device tensor of at least `ir_preprocess_ws_bytes(x.shape, len(stages))` bytes that a caller keeps across
+    calls ON ONE STREAM; allocated per call when None.  -> out (a new tensor unless given; never x)."""
+    _need_cuda(x, out, q_out, ws)
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("ir_preprocess: images must be a contiguous float32 [N, C, H, W] tensor (got %s %s, strides %s)"
+                         % (x.dtype, tuple(x.shape), tuple(x.stride())))
+    stages = [int(s) for s in stages]
+    N, Cc, H, W = x.shape
+    if Cc not in (1, 3) or N < 1 or N * Cc > 65535 or H < 2 or W < 2 or H * W > IRP_MAX_PIXELS or not 1 <= len(stages) <= IRP_MAX_STAGES:
+        raise ValueError(_irp_shape_msg(x.shape, len(stages)))
+    for s in stages:
+        if s < 0 or s >> 11 or (s & 255) > IRP_BLUR or not (s >> 8) & ((1 << Cc) - 1):
+            raise ValueError("ir_preprocess: stage 0x%x is not op | channel_mask << 8 with op in 0..3 and a mask naming a channel of a "
+                             "%d-channel batch" % (s, Cc))
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.dtype != torch.float32 or tuple(out.shape) != tuple(x.shape) or not out.is_contiguous() or out.data_ptr() == x.data_ptr():
+        raise ValueError("ir_preprocess: out must be a contiguous float32 tensor of shape %s, not the input itself" % (tuple(x.shape),))
+    if q_out is not None and (q_out.dtype != torch.float32 or tuple(q_out.shape) != (N, Cc, 2) or not q_out.is_contiguous()):
+        raise ValueError("ir_preprocess: q_out must be a contiguous float32 [%d, %d, 2] tensor" % (N, Cc))
+    lib = _abi.load()
+    need = ir_preprocess_ws_bytes(x.shape, len(stages))
+    if ws is None:
+        ws = torch.empty((need,), dtype=torch.uint8, device=x.device)
+    elif ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous():
+        raise ValueError("ir_preprocess: ws must be a contiguous uint8 tensor of at least %d bytes" % need)
+    arr = (C.c_int * len(stages))(*stages)
+    check(lib.hd_ir_preprocess(ptr(x), N, Cc, H, W, arr, len(stages), ptr(out), ptr(q_out), ptr(ws), _stream()), "hd_ir_preprocess")
+    return out
+
+
 # COCO mAP evaluation grid of hd_map_match / hd_map_accumulate (include/hallucidet_hip.h)
 MAP_NUM_IOU, MAP_NUM_AREA, MAP_NUM_MAXDET, MAP_NUM_REC = 10, 4, 3, 101
 MAP_MAX_DET, MAP_DET_CAP, MAP_GT_CAP = 100, 1024, 512

@@ -17,6 +17,7 @@ import torch
 from . import ops
 from .config import Config
 from .distributed import GradientAverager, broadcast_parameters
+from .models.cnnBasedThermalInfraredDA import IR_PREPROCESS_NAMES, CnnBasedThermalInfraredDA
 from .models.detector import Detector
 from .optim import FusedAdam, LossScaler, ParamArena
 from .utils.utils import Utils
@@ -24,13 +25,19 @@ from .utils.utils import Utils
 
 class DetectorLit:
     def __init__(self, batch_size=4, wandb_logger=None, lr=0.0001, detector_name='fasterrcnn', pretrained=True, optimizer_name='adam',
-                 modality=None, directly_coco=False, detector=None, device='cuda', loss_scale=1024.0, precision=16, map_device='cpu'):
+                 modality=None, directly_coco=False, detector=None, device='cuda', loss_scale=1024.0, precision=16, map_device='cpu',
+                 ir_preprocess='none'):
         if not any(k in detector_name for k in ('fasterrcnn', 'retinanet', 'fcos')):
             raise ValueError("unknown detector %r (fasterrcnn / retinanet / fcos)" % (detector_name,))
         self.wandb_logger, self.lr, self.batch_size = wandb_logger, lr, batch_size
         self.optimizer_name, self.detector_name, self.modality = optimizer_name, detector_name, modality
         self.dev = device
         self.map_device = map_device          # 'cpu': host COCO mAP evaluator (default); 'cuda': the HIP one (metrics/device.py)
+        # image-space baseline (models/cnnBasedThermalInfraredDA.py) applied to the image batch of all three splits: fine-tuning on
+        # pre-processed IR, the baseline HalluciDet is compared against
+        if ir_preprocess not in IR_PREPROCESS_NAMES:
+            raise ValueError("unknown ir_preprocess %r (one of %s)" % (ir_preprocess, ", ".join(IR_PREPROCESS_NAMES)))
+        self.ir_preprocess = ir_preprocess
         self.detector = detector if detector is not None else Detector(name=detector_name, pretrained=pretrained,
                                                                        n_classes=getattr(getattr(Config, 'Dataset', None), 'n_classes', 2), size=Config.Detector.input_size,
                                                                        modality=modality, directly_coco=directly_coco).detector
@@ -103,6 +110,8 @@ class DetectorLit:
                 imgs = Utils.expand_one_channel_to_output_channels(imgs, 3) if imgs.shape[1] == 1 else imgs
         else:
             imgs, targets, _, _ = batch
+        if self.ir_preprocess != 'none':
+            imgs = CnnBasedThermalInfraredDA.apply_preset(Utils.stack_images(imgs, device=self.dev), self.ir_preprocess)
         return imgs, Utils.batch_targets_for_detector(targets=targets, device=self.dev, detector_name=self.detector_name)
 
     def training_step(self, train_batch, batch_idx):

@@ -14,6 +14,7 @@ from . import ops
 from .config import Config
 from .distributed import GradientAverager, broadcast_parameters, exchange_and_step
 from .losses.losses import PixelTerms, Reconstruction
+from .models.cnnBasedThermalInfraredDA import IR_PREPROCESS_NAMES, CnnBasedThermalInfraredDA
 from .models.detector import Detector
 from .models.encoder_decoder import EncoderDecoder
 from .optim import LossScaler
@@ -50,7 +51,8 @@ class _WeightedLosses(torch.autograd.Function):
 class EncoderDecoderLit(nn.Module):
     def __init__(self, batch_size=4, wandb_logger=None, model_name='resnet34', in_channels=3, output_channels=3, lr=0.0001,
                  loss_pixel=None, loss_perceptual=None, detector_name='fasterrcnn', train_det=False, fuse_data='none',
-                 scheduler_on=False, detector=None, precision=16, device='cuda', use_graphs=True, map_device='cpu'):
+                 scheduler_on=False, detector=None, precision=16, device='cuda', use_graphs=True, map_device='cpu',
+                 ir_preprocess='none'):
         super().__init__()
         self.model_name, self.wandb_logger = model_name, wandb_logger
         self.in_channels, self.output_channels = in_channels, output_channels
@@ -62,6 +64,11 @@ class EncoderDecoderLit(nn.Module):
         self.dev = torch.device(device)
         # where the COCO mAP accumulators live: 'cpu' = the host evaluator (default), 'cuda' = the HIP one (metrics/device.py)
         self.map_device = map_device
+        # image-space baseline (models/cnnBasedThermalInfraredDA.py) applied to what the IR detector pass ("RGB Detector on IR") reads in
+        # validation and test; the U-Net input, the hallucinated pass, the pixel loss and the whole training step never see it
+        if ir_preprocess not in IR_PREPROCESS_NAMES:
+            raise ValueError("unknown ir_preprocess %r (one of %s)" % (ir_preprocess, ", ".join(IR_PREPROCESS_NAMES)))
+        self.ir_preprocess = ir_preprocess
         # src/losses/losses.py through train_hallucidet.py:115-116: 'mse' / 'l1' -> the HIP pixel loss (hd_pixel_loss), anything else
         # None; LPIPS raises (the `lpips` package and its weights are not available), the other perceptual names select nothing
         self.loss_pixel = Reconstruction.select_loss_pixel(loss_pixel=loss_pixel)
@@ -123,8 +130,11 @@ class EncoderDecoderLit(nn.Module):
             losses_det, loss_det_total, (detections_hall, detections_rgb, detections_ir) = graph.step(
                 imgs_hallucinated, imgs_rgb, imgs_ir_three_channel, targets_rgb, targets_ir)
         else:
+            imgs_ir_pass = imgs_ir_three_channel
+            if self.ir_preprocess != 'none' and step != 'train':
+                imgs_ir_pass = CnnBasedThermalInfraredDA.apply_preset(imgs_ir_three_channel, self.ir_preprocess)
             losses_det, loss_det_total, (detections_hall, detections_rgb, detections_ir) = self._detector_section(
-                imgs_hallucinated, imgs_rgb, imgs_ir_three_channel, targets_rgb, targets_ir, step, train_det)
+                imgs_hallucinated, imgs_rgb, imgs_ir_pass, targets_rgb, targets_ir, step, train_det)
         total_loss = loss_det_total
         if self.loss_pixel is not None:
             if 'pixel_rgb' in losses_det:           # computed inside the detector graph (not after a failed capture)

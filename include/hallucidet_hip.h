@@ -480,6 +480,40 @@ int hd_pixel_loss(const float* hall, const float* rgb, const float* ir, int N, i
 #define HD_AUG_MAX_PIXELS 16843009 /* 255 * H*W < 2^32 */
 int64_t hd_augment_u8_ws_bytes(int N, int C, int H, int W); /* < 0: bad shape (HD_E_ARG) */
 int hd_augment_u8(const uint8_t* x, const float* params, int N, int C, int H, int W, uint8_t* out, void* ws, void* stream);
+/* Image-space IR pre-processing baselines of the reference (src/models/cnnBasedThermalInfraredDA.py: invert, histogram stretching,
+ * histogram equalization, 3 x 3 Gaussian blur and their chains) on a planar fp32 batch (csrc/ir_preprocess.hip).
+ * x, out [N][C][H][W] fp32, C = 3 or 1, N*C <= 65535, H, W >= 2 (reflect padding), H*W <= HD_IRP_MAX_PIXELS (ranks are formed in
+ * fp32); out must not be x.  stages: a HOST array of n_stage (1..HD_IRP_MAX_STAGES) entries  op | channel_mask << 8  read during the
+ * call; bit c of the mask selects channel c, a channel outside a stage's mask passes through it; every operation works per image and
+ * per channel on the previous stage's output:
+ *   HD_IRP_INVERT    y = 1 - x
+ *   HD_IRP_STRETCH   q_min, q_max = the 0.003 and 1 - 0.003 quantiles of the plane as torch.quantile forms them (rank = fp32(q) *
+ *                    fp32(n - 1) in fp32, lo = floor(rank), hi = min(lo + 1, n - 1), linear interpolation between the two exact
+ *                    input elements of those ranks, found by radix select);  y = clamp((x - q_min) / (q_max - q_min), q_min, q_max):
+ *                    the reference clamps to the QUANTILES, not to [0, 1]; a constant plane gives 0/0 = NaN and stays NaN.
+ *                    Finite input only.
+ *   HD_IRP_EQUALIZE  u = trunc(x * 255) as uint8 (x in [0, 1]; other values are unspecified), torchvision's `equalize` on the
+ *                    256-bin histogram of the plane, y = float(lut[u]) / 255
+ *   HD_IRP_BLUR      torchvision's gaussian_blur with kernel 3 x 3, sigma 0.8, reflect padding; the nine fp32 products are summed
+ *                    in row-major tap order
+ * q_out: NULL, or [N][C][2] fp32 receiving (q_min, q_max) of the last stretch stage for the channels of its mask (others untouched).
+ * ws: hd_ir_preprocess_ws_bytes(N, C, H, W, n_stage) bytes of device memory, 16-byte aligned, contents irrelevant.
+ * The launch list depends on the stage list alone (inverts are folded into the neighbouring stage's read or write; a list of
+ * inverts is one pass; stretch = 4 x (histogram, resolve) + 1 pass, equalize = histogram + 1 pass, blur = 1 pass; one clearing launch): no host
+ * synchronisation, capturable; integer histograms only, so the result is the same bits from run to run.  Every fp32 step is a single
+ * IEEE operation (no contraction, true division).  With x / out 16-byte aligned the pointwise and histogram passes move 16 bytes per
+ * lane when H*W % 4 == 0 and the blur when W % 4 == 0; any other shape (127 x 161) takes the path of one float per lane.
+ * Null x / stages / out / ws, C not in {1, 3}, n_stage outside 1..4, an unknown op, a mask that names no channel of the batch,
+ * H or W < 2, H*W > HD_IRP_MAX_PIXELS, out == x -> HD_E_ARG. */
+#define HD_IRP_INVERT 0
+#define HD_IRP_STRETCH 1
+#define HD_IRP_EQUALIZE 2
+#define HD_IRP_BLUR 3
+#define HD_IRP_MAX_STAGES 4
+#define HD_IRP_MAX_PIXELS 16777216 /* 2^24 */
+int64_t hd_ir_preprocess_ws_bytes(int N, int C, int H, int W, int n_stage); /* < 0: bad shape (HD_E_ARG) */
+int hd_ir_preprocess(const float* x, int N, int C, int H, int W, const int* stages, int n_stage, float* out, float* q_out, void* ws,
+                     void* stream);
 /* COCO mAP on the device (hallucidet_amd/metrics/metrics.py `_evaluate_img` / `_accumulate`, restated bit for bit; csrc/coco_map.hip).
  * Fixed evaluation grid: 10 IoU thresholds, 4 area ranges (all, small, medium, large), max-dets 1 / 10 / 100, 101 recall thresholds. */
 #define HD_MAP_NUM_IOU 10

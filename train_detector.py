@@ -15,6 +15,9 @@ from hallucidet_amd.trainer import Trainer
 def main(argv=None):
     Config.set_environment()
     args = Config.argument_parser(argv)
+    if args.ir_preprocess != "none" and args.modality != "ir":
+        raise SystemExit("train_detector.py: --ir-preprocess %s pre-processes infrared images; it needs --modality ir (got --modality %s)"
+                         % (args.ir_preprocess, args.modality))
     torch.manual_seed(args.seed)
     dataset = args.dataset or "llvip"
     Config.set_detector(args.detector, train_det=False, pretrained=False, dataset=dataset)
@@ -31,7 +34,7 @@ def main(argv=None):
                                seed=args.seed, rank=rank, world_size=world, modality=args.modality)
     kw = dict(batch_size=args.batch, lr=1e-4 if args.lr is None else args.lr, detector_name=Config.Detector.name, pretrained=args.pretrained,
               modality=args.modality, directly_coco=args.directly_coco, device=dev, precision=args.precision,
-              map_device=args.map_device)
+              map_device=args.map_device, ir_preprocess=args.ir_preprocess)
     model = DetectorLit.load_from_checkpoint(args.pre_train_path, **kw) if args.pre_train_path else DetectorLit(**kw)
     model.prepare()
     out_dir = os.path.join("lightning_logs", args.wandb_project, args.wandb_name, "_".join([dataset, args.modality, Config.Detector.name]))

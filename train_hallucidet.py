@@ -15,9 +15,13 @@ from hallucidet_amd.train_hallucidet import EncoderDecoderLit
 from hallucidet_amd.trainer import Trainer
 
 
-def print_ap50(maps):
+def print_ap50(maps, ir_preprocess=None):
+    """`ir_preprocess`: the --ir-preprocess name the IR pass ran with; named on its line (None / 'none': the reference's three lines)."""
     g = lambda k: round(float(maps[k]["map_50"]) * 100, 2)
-    print("RGB Detector on IR  AP@50: ", g("map_ir"))
+    if ir_preprocess in (None, "none"):
+        print("RGB Detector on IR  AP@50: ", g("map_ir"))
+    else:
+        print("RGB Detector on IR (%s) AP@50: " % ir_preprocess, g("map_ir"))
     print("RGB Detector on RGB AP@50: ", g("map_rgb"))
     print("HalluciDet   on IR  AP@50: ", g("map_hall"))
 
@@ -46,7 +50,8 @@ def main(argv=None):
     kw = dict(batch_size=args.batch, model_name=args.decoder_backbone, in_channels=Config.EncoderDecoder.in_channels_encoder,
               output_channels=Config.EncoderDecoder.out_channels_decoder, lr=1e-4 if args.lr is None else args.lr,
               detector_name=Config.Detector.name, train_det=Config.Detector.train_det, fuse_data=args.fuse_data, precision=args.precision, device=dev,
-              loss_pixel=Config.Losses.pixel, loss_perceptual=Config.Losses.perceptual, map_device=args.map_device)
+              loss_pixel=Config.Losses.pixel, loss_perceptual=Config.Losses.perceptual, map_device=args.map_device,
+              ir_preprocess=args.ir_preprocess)
     model = EncoderDecoderLit.load_from_checkpoint(args.pre_train_path, strict=False, **kw) if args.pre_train_path else EncoderDecoderLit(**kw)
     if args.detector_path:
         from hallucidet_amd.checkpoint import load_detector
@@ -58,7 +63,7 @@ def main(argv=None):
     tr.fit(model, dm)
     if rank == 0:
         tr.save_checkpoint(model, os.path.join(out_dir, "encoder_decoder_pl.ckpt"))
-        print_ap50(tr.test(model, dm))
+        print_ap50(tr.test(model, dm), ir_preprocess=args.ir_preprocess)
     if world > 1:
         torch.distributed.destroy_process_group()
 
