@@ -12,6 +12,7 @@
 // K order: tap-major, 16 channels at a time -- the order the implicit-GEMM kernels accumulate in.
 #include "hd_common.h"
 #include "conv_params.h"
+#include "hd_lds_dma.h"
 #include <stdlib.h>
 
 namespace {
@@ -23,13 +24,6 @@ constexpr int PPW = (NPIECE + 3) / 4;                // 3 pieces per wave
 constexpr int STAGE_BYTES = 4 * PPW * 1024;          // 12 KiB
 constexpr int KSTEPS = 18, KROW = 288;
 constexpr int LDS_BYTES = 2 * STAGE_BYTES;
-constexpr unsigned OOBB = 0x80000000u;
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, char* lds_dst, unsigned voff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void*)lds_dst, 16, voff, 0, 0, 0);
-}
 
 #define HD_C32_MFMA0_A(ACC, WF, BF) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(ACC) : "a"(WF), "v"(BF))
 #define HD_C32_MFMA_A(ACC, WF, BF) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(ACC) : "a"(WF), "v"(BF))
@@ -46,11 +40,7 @@ __global__ __launch_bounds__(256) void conv3x3_c32to128_kernel(ConvP p, int tile
   const int h = lane >> 5, pl = lane & 31;
 
   const int G = gridDim.x;
-  int L;
-  {
-    const int b = blockIdx.x, xcd = b & 7, qq = G >> 3, rr = G & 7;
-    L = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (b >> 3);
-  }
+  const int L = hd_xcd_contiguous(blockIdx.x, G);
   const int t_begin = (int)((long long)L * tiles_total / G), t_end = (int)((long long)(L + 1) * tiles_total / G);
   const int tiles_x = (p.Wo + TW - 1) / TW, tiles_y = (p.Ho + TH - 1) / TH;
   const int H = p.Hin, W = p.Win;

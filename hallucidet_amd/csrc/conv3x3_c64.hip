@@ -22,6 +22,7 @@
 // K order is tap-major, 16 channels at a time -- the order the implicit-GEMM kernels accumulate in.
 #include "hd_common.h"
 #include "conv_params.h"
+#include "hd_lds_dma.h"
 #include <stdlib.h>
 
 namespace {
@@ -37,13 +38,6 @@ constexpr int LDS_BYTES = W_OFF + W_BYTES;       // 120 KiB: one block per CU
 constexpr int CF_OFF = W_OFF + 4 * 64 * 65 * 4;  // per-channel coefficients of the bs_* modes: behind the statistics transpose, inside the weight staging
 constexpr int BIAS_OFF = CF_OFF + 4 * 64 * 4;    // the bias vector (EPI & 2): read per tile from LDS, not from memory
 static_assert(BIAS_OFF + 64 * 4 <= LDS_BYTES, "coefficient table and bias fit");
-constexpr unsigned OOBB = 0x80000000u;
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, char* lds_dst, unsigned voff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void*)lds_dst, 16, voff, 0, 0, 0);
-}
 
 // The MFMAs are inline assembly so that the weight fragments can be PINNED in the accumulator file ("a" operands: 64 of the 72 fragments
 // = all 256 AGPRs; the last 8 stay in VGPRs): left to the register allocator they were spilled to AGPRs and copied back with four
@@ -78,14 +72,10 @@ __global__ __launch_bounds__(256) void conv3x3_c64_kernel(ConvP p, int tiles_tot
 #define TR_MARK(accu) do {} while (0)
 #endif
 
-  // blocks are dealt round-robin over the 8 XCDs: give each XCD a contiguous eighth of the tile list and each block a contiguous run
-  // (neighbouring tiles share their halo columns in that XCD's L2)
+  // each XCD gets a contiguous eighth of the tile list and each block a contiguous run (neighbouring tiles share their halo columns in
+  // that XCD's L2)
   const int G = gridDim.x;
-  int L;
-  {
-    const int b = blockIdx.x, xcd = b & 7, qq = G >> 3, rr = G & 7;
-    L = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (b >> 3);
-  }
+  const int L = hd_xcd_contiguous(blockIdx.x, G);
   const int t_begin = (int)((long long)L * tiles_total / G), t_end = (int)((long long)(L + 1) * tiles_total / G);
   const int tiles_x = (p.Wo + TW - 1) / TW, tiles_y = (p.Ho + TH - 1) / TH;
   const int H = p.Hin, W = p.Win;

@@ -49,6 +49,7 @@
 // (s % 5, weights four steps ahead; five does not divide the 18-step table), everything else -- roles, hazards, swizzle -- as above.
 #include "hd_common.h"
 #include "conv_params.h"
+#include "hd_lds_dma.h"
 #include "conv_w8_epilogue.h"
 
 namespace {
@@ -80,12 +81,6 @@ struct M160 {
   static_assert(LDS_HALVES * 2 <= 160 * 1024, "LDS");
 };
 
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, f16* lds_dst, unsigned voff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void*)lds_dst, 16, voff, 0, 0, 0);
-}
-
 template <int TH, int TW, bool DUAL>
 __device__ __forceinline__ void conv3x3_m160_body(ConvP& p, f16* lds, int bid_in, int nwg_in) {
   using G = M160<TH, TW>;
@@ -102,13 +97,9 @@ __device__ __forceinline__ void conv3x3_m160_body(ConvP& p, f16* lds, int bid_in
   HD_TRACE(0, wall_clock64());
   HD_TRACE(1, clock64());
 
-  int bid = bid_in;
-  {
-    // blocks are dealt round-robin over the 8 XCDs: give each XCD a contiguous run of the tile list (N tiles fastest: the four / two
-    // channel tiles of a pixel tile share its patch in that XCD's L2)
-    const int nwg = nwg_in, xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
-    bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
-  }
+  // each XCD gets a contiguous run of the tile list (N tiles fastest: the four / two channel tiles of a pixel tile share its patch in
+  // that XCD's L2)
+  const int bid = hd_xcd_contiguous(bid_in, nwg_in);
   const int tile_m = bid / p.gn, tile_n = bid - tile_m * p.gn;
   const int tiles_x = (p.Wo + TW - 1) / TW, tiles_y = (p.Ho + TH - 1) / TH;
   const int n_img = tile_m / (tiles_x * tiles_y);
@@ -149,9 +140,8 @@ __device__ __forceinline__ void conv3x3_m160_body(ConvP& p, f16* lds, int bid_in
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(p.x), 0, p.xbytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rx2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(DUAL ? p.x2 : p.x), 0, DUAL ? p.x2bytes : p.xbytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(p.w), 0, p.wbytes, 0x00020000);
-    // An out-of-range lane keeps its offset at >= 2^31 whatever uniform offset is added later (all tensors here are < 2 GiB: checked by
-    // hd_conv_m160_eligible), so the per-step address of a piece is ONE v_add and the hardware zero-fills.
-    constexpr unsigned OOBB = 0x80000000u;
+    // OOBB (hd_lds_dma.h): all tensors here are < 2 GiB (checked by hd_conv_m160_eligible), so the per-step address of a piece is ONE
+    // v_add and the hardware zero-fills.
     // ---- patch fill: piece k of this wave is piece k * 4 + pw of the chunk; fixed pixel / slot per lane for the whole K loop
     unsigned pb1[PK], pb2[PK];
 #pragma unroll

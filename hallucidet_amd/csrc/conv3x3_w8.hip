@@ -28,20 +28,14 @@
 //     they keep the sub-step split (HD_W8_TS=2 forces it everywhere; profiles/r05_probe_w8_ts.txt).
 #include "hd_common.h"
 #include "conv_params.h"
+#include "hd_lds_dma.h"
 #include "wgrad3x3_w8_body.h"
 #include "conv_w8_epilogue.h"
 
 namespace {
 
 constexpr int LDS_ROW = 64;   // halves per weight row per K step (128 B)
-constexpr unsigned OOB = 0xFFFFFFF0u;
 constexpr int TW = 8, PW = 10;
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, f16* lds_dst, unsigned voff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void*)lds_dst, 16, voff, 0, 0, 0);
-}
 
 __device__ __forceinline__ int swz_of(int y, int x) { return ((x >> 1) + 4 * y) & 7; }
 
@@ -90,11 +84,7 @@ __device__ __forceinline__ void conv3x3_w8_body(ConvP& p, f16* lds, int bid_in, 
   HD_TRACE(0, wall_clock64());
   HD_TRACE(1, clock64());
 
-  int bid = bid_in;
-  {
-    const int nwg = nwg_in, xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
-    bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
-  }
+  const int bid = hd_xcd_contiguous(bid_in, nwg_in);
   const int tile_m = bid / p.gn, tile_n = bid - tile_m * p.gn;
   const int tiles_x = (p.Wo + TW - 1) / TW, tiles_y = (p.Ho + TH - 1) / TH;
   const int n_img = tile_m / (tiles_x * tiles_y);
@@ -107,9 +97,8 @@ __device__ __forceinline__ void conv3x3_w8_body(ConvP& p, f16* lds, int bid_in, 
   const __amdgpu_buffer_rsrc_t rx2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(DUAL ? p.x2 : p.x), 0, DUAL ? p.x2bytes : p.xbytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(p.w), 0, p.wbytes, 0x00020000);
 
-  // An out-of-range lane keeps its offset at >= 2^31 whatever uniform offset is added later (all tensors here are < 2 GiB:
-  // checked by hd_conv_p8_eligible), so the per-step address of a piece is ONE v_add and the hardware zero-fills.
-  constexpr unsigned OOBB = 0x80000000u;
+  // OOBB (hd_lds_dma.h): all tensors here are < 2 GiB (checked by hd_conv_p8_eligible), so the per-step address of a piece is ONE
+  // v_add and the hardware zero-fills.
   // ---- patch fill: piece k of this wave is piece k*8 + wave of the chunk; fixed pixel / slot per lane for the whole K loop
   unsigned pb1[PPW], pb2[PPW];
 #pragma unroll

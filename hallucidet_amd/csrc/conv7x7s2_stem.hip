@@ -14,6 +14,7 @@
 // K order: tap-major, 8 channels per tap (tap 49 is a zero row) -- the order of the weight layout [64][7*7*8].
 #include "hd_common.h"
 #include "conv_params.h"
+#include "hd_lds_dma.h"
 #include <stdlib.h>
 
 namespace {
@@ -28,13 +29,6 @@ constexpr int KSTEPS = 25, NTAP = 49, KROW = NTAP * 8;
 constexpr int RED_OFF = 2 * STAGE_BYTES;             // statistics transpose [4 waves][64][65] floats
 constexpr int BIAS_OFF = RED_OFF + 4 * 64 * 65 * 4;  // the bias vector (EPI & 2): read per tile from LDS, not from memory
 constexpr int LDS_BYTES = BIAS_OFF + 64 * 4;
-constexpr unsigned OOBB = 0x80000000u;
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, char* lds_dst, unsigned voff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void*)lds_dst, 16, voff, 0, 0, 0);
-}
 
 #define HD_STEM_MFMA0(ACC, WF, BF) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(ACC) : "a"(WF), "v"(BF))
 #define HD_STEM_MFMA(ACC, WF, BF) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(ACC) : "a"(WF), "v"(BF))
@@ -54,11 +48,7 @@ __global__ __launch_bounds__(256) void conv7x7s2_stem_kernel(ConvP p, int tiles_
   const int h = lane >> 5, pl = lane & 31;
 
   const int G = gridDim.x;
-  int L;
-  {
-    const int b = blockIdx.x, xcd = b & 7, qq = G >> 3, rr = G & 7;
-    L = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (b >> 3);
-  }
+  const int L = hd_xcd_contiguous(blockIdx.x, G);
   const int t_begin = (int)((long long)L * tiles_total / G), t_end = (int)((long long)(L + 1) * tiles_total / G);
   const int tiles_x = (p.Wo + TW - 1) / TW, tiles_y = (p.Ho + TH - 1) / TH;
   const int H = p.Hin, W = p.Win;

@@ -1,4 +1,5 @@
-// hd_conv2d entry point: argument checks, tile / K-depth selection, dispatch to the two kernel families
+// hd_conv2d entry point: argument checks, tile / K-depth selection, dispatch to the two depths of the implicit-GEMM family
+// (one body, conv_igemm_body.h, instantiated by)
 //   conv_igemm_bk32.hip : 32-deep K tiles (half-line DMA pieces; any Cin % 8 == 0; the 16/32-channel layers)
 //   conv_igemm_bk64.hip : 64-deep K tiles (full 128-byte-line DMA pieces, one barrier per 16 MFMAs; Cin % 64 == 0)
 #include <stdlib.h>
@@ -147,7 +148,7 @@ extern "C" int hd_conv_tune_override(int bm, int bn, int bk, int deep) {
 }
 
 #ifdef HD_CONV_TRACE
-// profiling build only (not part of the shipped ABI): where the 64-deep kernels write their per-block stamps
+// profiling build only (not part of the shipped ABI): where the kernels with HD_TRACE stamps (the implicit-GEMM family at both K depths among them) write their 16 stamps per block
 static unsigned long long* g_trace = nullptr;
 extern "C" int hd_conv_trace_buffer(void* buf) {
   g_trace = (unsigned long long*)buf;

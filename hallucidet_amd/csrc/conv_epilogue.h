@@ -1,4 +1,4 @@
-// Epilogue shared by the implicit-GEMM convolution kernels (conv_igemm_bk32.hip / conv_igemm_bk64.hip):
+// Epilogue shared by the implicit-GEMM convolution kernels (conv_igemm_body.h):
 //   y = act( mask( acc (+ residual) + bias ) ),  optional per-tile BatchNorm partial sums of the f16-rounded pre-activation.
 //
 // Vector path (NHWC f16 output, Cout % 8 == 0): accumulators -> LDS fp32 tile -> each thread owns 8 consecutive output

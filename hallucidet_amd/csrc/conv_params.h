@@ -1,4 +1,4 @@
-// Shared parameter block of the implicit-GEMM convolution kernels (conv_igemm_bk32.hip / conv_igemm_bk64.hip).
+// Shared parameter block of the implicit-GEMM convolution kernels (conv_igemm_body.h) and of the kernels that share its dispatcher.
 #pragma once
 #include <stdlib.h>
 

@@ -9,30 +9,24 @@
 // BM * BN / 32 MFMA clocks, so 128x64 is fill-bound at 34 % MFMA utilisation, 128x128 at 52 %, 256x128 at 69 % and only 256x256
 // balances the two.  The 4-wave kernels stop at 128x128 (fc6: 0.85 PFLOP/s forward, 0.44 data gradient = 6 272 tiles of 128x64, each
 // re-filling 393 KB for 16 K steps).  This kernel: 256 x 128 tile on 8 waves (three 48-KB LDS stages) or 128 x 128 on 4 waves (two 32-KB
-// stages, two blocks per CU), 64-deep K steps, filled by LDS-DMA exactly as conv_igemm_bk64.hip fills its (same piece shape, same source-side swizzle, zero-fill by
+// stages, two blocks per CU), 64-deep K steps, filled by LDS-DMA exactly as the 64-deep implicit-GEMM kernels (conv_igemm_body.h, BK = 64) fill theirs (same piece shape, same source-side swizzle, zero-fill by
 // out-of-range buffer offsets), one barrier per K step.
 //   * The WEIGHTS are the MFMA A operand (rows of the 32x32 result = output channels), the activations the B operand (columns =
 //     GEMM rows): a lane then owns 4 consecutive channels of one output row per register group, `v_permlane32_swap` pairs two groups
 //     into 8 channels = one 16-byte store -- the epilogue stays in registers (no fp32 tile through LDS, no barrier), bias / ReLU
 //     before the rounding, the ReLU-backward mask on the packed result (masking commutes with rounding).
-//   * Products and their fp32 summation order over K are those of conv_igemm_bk64.hip (k = 64 kt + 16 ks + 8 h + j, one chain per
+//   * Products and their fp32 summation order over K are those of the 64-deep implicit-GEMM kernels (k = 64 kt + 16 ks + 8 h + j, one chain per
 //     output), so the result is bit-identical to that family's -- which tile runs a problem may depend on the batch size
 //     (tests/test_kernels_gpu.py::test_gemm_w8_matches_the_igemm_family_bit_for_bit).
 //   * Tile list: XCD-contiguous runs in grouped order (conv_params.h: hd_conv_tile_order), the group sized from the operand bytes.
 #include "hd_common.h"
 #include "conv_params.h"
+#include "hd_lds_dma.h"
 
 namespace {
 
 constexpr int GK = 64;             // K step
 constexpr int GROW = 64;           // halves per LDS row (128 bytes)
-constexpr unsigned GOOB = 0xFFFFFFF0u;
-
-typedef __attribute__((address_space(3))) void lds_void_g;
-
-__device__ __forceinline__ void gdma16(__amdgpu_buffer_rsrc_t r, f16* lds_dst, unsigned voff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_g*)lds_dst, 16, voff, 0, 0, 0);
-}
 
 // BM: rows of x (GEMM M) per tile, BN: rows of w (output channels) per tile.  Waves = 2 (channels) x BM / 64 (rows): a wave owns
 // BN / 2 channels x 64 rows -- 8 waves at BM = 256, 4 at BM = 128 (the 128 x 128 tile: two blocks per CU, for the short-K 1x1 layers
@@ -54,11 +48,7 @@ __global__ __launch_bounds__(128 * (BM / 64)) void gemm_w8_kernel(ConvP p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wn = wave / NWM, wm = wave - wn * NWM;
 
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x, xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
-    bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
-  }
+  const int bid = hd_xcd_contiguous(blockIdx.x, gridDim.x);
   int tile_m, tile_n;
   hd_conv_tile_of(p, bid, tile_m, tile_n);
   const int m0 = tile_m * BM, n0 = tile_n * BN;
@@ -92,9 +82,9 @@ __global__ __launch_bounds__(128 * (BM / 64)) void gemm_w8_kernel(ConvP p) {
     const bool kv = kt_issue * GK + j * 8 < K;           // K % 8 == 0: a 16-byte chunk is inside or outside as a whole
     const unsigned ko = (unsigned)kt_issue * (GK * 2);
 #pragma unroll
-    for (int i = 0; i < W_PASS; ++i) gdma16(rw, sw + i * (RP * GROW), (wok[i] && kv) ? wbase[i] + ko : GOOB);
+    for (int i = 0; i < W_PASS; ++i) dma16(rw, sw + i * (RP * GROW), (wok[i] && kv) ? wbase[i] + ko : OOB);
 #pragma unroll
-    for (int i = 0; i < X_PASS; ++i) gdma16(rx, sx + i * (RP * GROW), (xok[i] && kv) ? xbase[i] + ko : GOOB);
+    for (int i = 0; i < X_PASS; ++i) dma16(rx, sx + i * (RP * GROW), (xok[i] && kv) ? xbase[i] + ko : OOB);
     ++kt_issue;
   };
 

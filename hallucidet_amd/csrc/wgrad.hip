@@ -1,5 +1,5 @@
 // Weight-gradient implicit GEMM on MFMA:  dW[co][kk] = sum_pix dY[pix][co] * Xg[pix][kk]
-// (kk = (kh*KW+kw)*Cin + ci walks the same 16-byte chunk order as conv_igemm).
+// (kk = (kh*KW+kw)*Cin + ci walks the same 16-byte chunk order as conv_igemm_body.h).
 //
 // Both operands live in memory as [pixel][channel] (NHWC), i.e. the reduction index
 // is the SLOW axis.  Tiles are staged to LDS in that natural layout and the MFMA
@@ -14,6 +14,7 @@
 #include <stdlib.h>
 
 #include "hd_common.h"
+#include "hd_lds_dma.h"
 
 namespace {
 
@@ -91,7 +92,6 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgP p) {
   const __amdgpu_buffer_rsrc_t rdy = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(p.dy), 0, p.dybytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(p.x), 0, p.xbytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rx2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(p.x2 ? p.x2 : p.x), 0, p.x2 ? p.x2bytes : p.xbytes, 0x00020000);
-  constexpr unsigned OOB = 0xFFFFFFF0u;
   const bool first_src = bc < p.C1;
 
   // incremental pixel walk for the B (gather) rows: pixel index advances by BP per tile
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgP p) {
     const f16* sa = lds + buf * STAGE;
     const f16* sb = sa + BP * RSA;
     // both K sub-steps' fragments are requested before the first MFMA (two register sets, pinned by the scheduling barriers: the
-    // compiler otherwise re-uses one set and waits for the LDS in the middle of every sub-step; see conv_igemm_bk64.hip)
+    // compiler otherwise re-uses one set and waits for the LDS in the middle of every sub-step; see conv_igemm_body.h)
     f16x8 af[2][MT], bf[2][NT];
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {

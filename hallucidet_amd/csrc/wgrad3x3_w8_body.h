@@ -21,6 +21,7 @@
 //   * one fp32 partial per block -> slab[slice][co][tap*Cin + ci], summed by hd_wgrad_reduce (deterministic, as before).
 #pragma once
 #include "hd_common.h"
+#include "hd_lds_dma.h"
 #include <type_traits>
 
 namespace hd_wg8 {
@@ -34,7 +35,6 @@ constexpr int YSTAGE = YPIECES * 512;
 constexpr int STAGE = XSTAGE + YSTAGE;
 constexpr int NPIECES = XPIECES + YPIECES;      // 39 per tile
 constexpr int PPWV = (NPIECES + 7) / 8;         // 5 per wave
-constexpr unsigned OOBB = 0x80000000u;
 
 struct Wg8P {
   const f16* x;
@@ -48,12 +48,8 @@ struct Wg8P {
   unsigned xbytes, x2bytes, dybytes;
 };
 
-typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, f16* lds_dst, unsigned voff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void*)lds_dst, 16, voff, 0, 0, 0);
-}
 __device__ __forceinline__ f16x8 tr_pair(const char* p0, const char* p1) {
   s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0));
   s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p1));

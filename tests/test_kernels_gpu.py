@@ -1187,6 +1187,98 @@ def test_conv_small_channel_kernel_equals_igemm(dev, case):
     assert torch.allclose(stats.sum(0), rstats.sum(0), rtol=2e-3, atol=2e-2)
 
 
+# every (bm, bn, bk, deep) that hd_conv_tune_override accepts AND choose_tile (conv_dispatch.hip) leaves as given: the 32-wide N tile
+# exists only with 128 rows, 32-deep and two stages (bm, bk and deep are rewritten), so it appears once
+IGEMM_FORCED = [(128, 32, 32, 0)] + [(bm, bn, bk, deep) for bm in (64, 128) for bn in (64, 128) for bk in (32, 64) for deep in (0, 1)]
+_IGEMM_SWEEP = {}
+
+
+def _igemm_sweep_problems():
+    """Inputs and oracle results of the forced-variant sweep (CPU tensors, computed once, never written to)."""
+    if _IGEMM_SWEEP:
+        return _IGEMM_SWEEP
+    bias_of = lambda c, seed: torch.randn(c, generator=torch.Generator().manual_seed(seed))
+
+    def fwd(N, H, W, C1, C2, Cout, K, pad, up1, act, use_bias, use_res, seed):
+        x = rnd(N, H, W, C1, seed=seed)
+        Ho, Wo = (2 * H, 2 * W) if up1 else (H, W)                 # (stride 1, pad = K // 2: the extent stays)
+        x2 = rnd(N, Ho, Wo, C2, seed=seed + 1) if C2 else None
+        Kt = K * K * (C1 + C2)
+        w = rnd(Cout, Kt, scale=1.0 / math.sqrt(Kt), seed=seed + 2)
+        bias = bias_of(Cout, seed + 3) if use_bias else None
+        res = rnd(N, Ho, Wo, Cout, seed=seed + 4) if use_res else None
+        want, _ = ok.conv2d_nhwc(x, w, K, K, x2=x2, bias=bias, res=res, stride=1, pad=pad, up1=up1, act=act)
+        return dict(x=x, w=w, K=K, x2=x2, bias=bias, res=res, pad=pad, up1=up1, act=act, want=want.half(), pixels=N * Ho * Wo)
+
+    # M = 126 ragged inside one tile, ragged Cout, uniform-tap path, full epilogue
+    _IGEMM_SWEEP["ragged"] = fwd(2, 9, 7, 64, 0, 72, 3, 1, False, 1, True, True, 100)
+    # nk = 2 (32-deep) / 1 (64-deep): shorter than the prologue of every deep variant, whose out-of-range tiles must arrive as zeros
+    _IGEMM_SWEEP["short_k"] = fwd(2, 5, 5, 64, 0, 40, 1, 0, False, 0, False, False, 110)
+    # Cin = 24: per-lane taps (KGEN); not a multiple of 64, so 32-deep only
+    _IGEMM_SWEEP["kgen"] = fwd(1, 10, 10, 24, 0, 64, 3, 1, False, 0, False, False, 120)
+    # dual source: 4 x 5 upsampled to 8 x 10, K tiles on both sides of the concat boundary
+    _IGEMM_SWEEP["dual"] = fwd(1, 4, 5, 64, 64, 48, 3, 1, True, 0, False, False, 130)
+    # three problems of different sizes for hd_conv2d_multi (one weight tensor, as a head over three pyramid levels)
+    _IGEMM_SWEEP["multi"] = [fwd(n, h, w_, 64, 0, 72, 3, 1, False, 1, True, False, 140) for n, h, w_ in ((2, 9, 7), (1, 5, 5), (1, 3, 4))]
+    # the smallest (fewest multiply-adds) stride-2 entry of DGRAD_CASES with Cin % 64 == 0; the kernel's own reduction runs over the
+    # forward Cout, which must be a multiple of 64 too for the 64-deep variants to take it
+    N, H, W, Cin, Cout, K, stride, pad = min((c for c in DGRAD_CASES if c[6] == 2 and c[3] % 64 == 0),
+                                             key=lambda c: c[0] * c[1] * c[2] * c[3] * c[4] * c[5] * c[5])
+    assert Cout % 64 == 0
+    w_oihw = torch.randn(Cout, Cin, K, K, generator=torch.Generator().manual_seed(150)) / math.sqrt(K * K * Cin)
+    Ho, Wo = (H + 2 * pad - K) // stride + 1, (W + 2 * pad - K) // stride + 1
+    dy = rnd(N, Ho, Wo, Cout, seed=151)
+    w_flat = w_oihw.half().float().permute(0, 2, 3, 1).reshape(Cout, K * K * Cin)
+    want = ok.conv2d_dgrad_nhwc(dy, w_flat, K, K, Cin, stride=stride, pad=pad, in_hw=(H, W))
+    _IGEMM_SWEEP["dgrad"] = dict(dy=dy, w_oihw=w_oihw, K=K, stride=stride, pad=pad, hw=(H, W), cin=Cin, want=want.half())
+    return _IGEMM_SWEEP
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bm,bn,bk,deep", IGEMM_FORCED)
+def test_igemm_every_forced_variant_matches_the_oracle(dev, bm, bn, bk, deep):
+    """Every variant of the implicit-GEMM family (conv_igemm_body.h: tile x K depth x stage count), forced through the tuning
+    override, against oracle.kernels on the smallest problems at which each of its paths can go wrong.  Where statistics are
+    returned their row count cdiv(pixels, bm) shows that the forced tile really ran.  What the dispatcher does under ANY override
+    (conv_dispatch.hip, g_small_ok): a stride-2 data gradient runs as the zero-dilated walk, not as parity classes, and
+    hd_conv2d_multi issues its problems one by one -- so those two cases cover the forced variant's single-problem kernel; the
+    parity classes and the multi-problem grid of the variants the heuristic picks are covered by test_conv2d_dgrad and
+    test_conv2d_multi_equals_separate_calls."""
+    from hallucidet_amd import ops, _abi
+    P = _igemm_sweep_problems()
+    d = lambda t: None if t is None else t.to(dev)
+    lib = _abi.load()
+
+    def call(q, want_stats=True):
+        return ops.conv2d(d(q["x"]), d(q["w"]), q["K"], q["K"], x2=d(q["x2"]), bias=d(q["bias"]), res=d(q["res"]), pad=q["pad"],
+                          up1=q["up1"], act=q["act"], want_stats=want_stats)
+
+    dg = P["dgrad"]
+    _, wd = ops.weight_prep(dg["w_oihw"].to(dev), want_fwd=False, want_dgrad=True)
+    assert lib.hd_conv_tune_override(bm, bn, bk, deep) == 0
+    try:
+        for name in ("ragged", "short_k", "kgen", "dual"):
+            if name == "kgen" and bk == 64:
+                continue
+            q = P[name]
+            got, stats = call(q)
+            assert got.shape == q["want"].shape, name
+            close(got, q["want"])
+            assert stats.shape[0] == (q["pixels"] + bm - 1) // bm, name
+        K = dg["K"]
+        got = ops.conv2d(d(dg["dy"]), wd, K, K, stride=1, pad=K - 1 - dg["pad"], in_dil=dg["stride"], out_hw=dg["hw"], cout=dg["cin"])
+        assert got.shape == dg["want"].shape
+        close(got, dg["want"])
+        calls = [(d(q["x"]), d(q["w"]), q["K"], q["K"], dict(bias=d(q["bias"]), pad=q["pad"], act=q["act"])) for q in P["multi"]]
+        sep = [ops.conv2d(x, w, kh, kw, **kw_) for x, w, kh, kw, kw_ in calls]
+        for q, a, b in zip(P["multi"], sep, ops.conv2d_multi(calls)):
+            assert torch.equal(a, b)
+            close(b, q["want"])
+        torch.cuda.synchronize()
+    finally:
+        lib.hd_conv_tune_override(-1, -1, -1, -1)
+
+
 @pytest.mark.gpu
 def test_fused_detector_losses_equal_torch_ops(dev):
     """hd_rpn_loss / hd_fastrcnn_loss (+ backward) against the torch-op forms they replace: loss values to fp32 summation
