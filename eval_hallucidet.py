@@ -9,7 +9,7 @@ from hallucidet_amd.config import Config
 from hallucidet_amd.dataloader import MultiModalDataModule
 from hallucidet_amd.train_hallucidet import EncoderDecoderLit
 from hallucidet_amd.trainer import Trainer
-from train_hallucidet import print_ap50
+from train_hallucidet import media_writer, print_ap50
 
 
 def main(argv=None):
@@ -27,7 +27,7 @@ def main(argv=None):
                               ext=args.ext or ".jpg", seed=args.seed)
     kw = dict(batch_size=args.batch, model_name=args.decoder_backbone, detector_name=Config.Detector.name, precision=args.precision, device=dev,
               loss_pixel=Config.Losses.pixel, loss_perceptual=Config.Losses.perceptual, map_device=args.map_device,
-              ir_preprocess=args.ir_preprocess)
+              ir_preprocess=args.ir_preprocess, media=media_writer(args))
     model = EncoderDecoderLit.load_from_checkpoint(args.hallucidet_path, strict=False, **kw) if args.hallucidet_path else EncoderDecoderLit(**kw)
     if args.detector_path:
         from hallucidet_amd.checkpoint import load_detector
@@ -36,6 +36,8 @@ def main(argv=None):
     model.detector.to(dev)
     model.eval()            # Lightning's test loop: BatchNorm on the checkpoint's running statistics, detector in eval mode
     maps = Trainer(device=dev).test(model, dm)
+    if model.media is not None:
+        model.media.close()
     print_ap50(maps, ir_preprocess=args.ir_preprocess)
     return maps
 

@@ -156,7 +156,9 @@ PROTOTYPES = {
     "hd_augment_u8": (C.c_int, [vp, vp] + [C.c_int] * 4 + [vp, vp, vp]),
     "hd_ir_preprocess_ws_bytes": (c_i64, [C.c_int] * 5),
     "hd_ir_preprocess": (C.c_int, [vp] + [C.c_int] * 4 + [C.POINTER(C.c_int), C.c_int, vp, vp, vp, vp]),
-    "hd_map_match": (C.c_int, [vp] * 4 + [C.c_int] * 2 + [vp] * 3 + [C.c_int, vp, C.c_int] + [vp] * 9),
+    "hd_media_ws_bytes": (c_i64, [C.c_int]),
+    "hd_media_render": (C.c_int, [vp, c_i64, c_i64] + [C.c_int] * 5 + [vp, C.c_int, vp, vp, C.c_int, c_f, vp, vp, C.c_int, vp, vp, vp]),
+    "hd_map_match":(C.c_int, [vp] * 4 + [C.c_int] * 2 + [vp] * 3 + [C.c_int, vp, C.c_int] + [vp] * 9),
     "hd_map_accumulate": (C.c_int, [vp, vp, vp, c_i64, vp, vp, C.c_int, vp, vp, vp, vp]),
     "hd_sample_pos_neg": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "hd_roi_postprocess": (C.c_int, [vp, vp, vp, C.c_long, vp, C.c_int, C.c_int, C.c_int, vp] + [C.c_float] * 5 + [vp] * 4),

@@ -127,6 +127,12 @@ class Config:
         # train_detector.py --modality ir what the detector is fine-tuned and evaluated on
         from .models.cnnBasedThermalInfraredDA import IR_PREPROCESS_NAMES
         p.add_argument("--ir-preprocess", type=str, default="none", choices=list(IR_PREPROCESS_NAMES))
+        # detection media (utils/media.py): validation / test write the reference's panels (inputs, hallucinated output, the three "det"
+        # panels with ground truths in yellow and detections above --threshold in red) as PNG grids under DIR, every N-th batch at the
+        # reference's phase (batch_idx % N == 1 % N), at most K batches per split and epoch.  Default: off
+        p.add_argument("--save-media", type=str, default=None, metavar="DIR")
+        p.add_argument("--media-every", type=int, default=100, metavar="N")
+        p.add_argument("--media-max", type=int, default=None, metavar="K")
         p.add_argument("--perceptual", type=str, default=None)
         p.add_argument("--weight-perceptual-rgb", type=float, default=0.0)
         p.add_argument("--weight-perceptual-ir", type=float, default=0.0)

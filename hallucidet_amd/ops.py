@@ -1231,6 +1231,157 @@ def ir_preprocess(x, stages, out=None, q_out=None, ws=None):
     return out
 
 
+MEDIA_QUANTISE, MEDIA_NORMALISE = 0, 1          # HD_MEDIA_* modes of hd_media_render
+MEDIA_MODES = {"quantise": MEDIA_QUANTISE, "normalise": MEDIA_NORMALISE}
+MEDIA_MAX_SIDE, MEDIA_DET_CAP, MEDIA_GT_CAP = 1499, 1024, 512
+
+
+def media_canvas_shape(shape, nrow=8):
+    """(CH, CW, 3) of the grid image of a batch of `shape` = (N, 3, H, W): torchvision's make_grid(nrow, padding=2), no padding for N = 1."""
+    N, _, H, W = (int(v) for v in shape)
+    xmaps = min(int(nrow), N)
+    ymaps = -(-N // xmaps)
+    pad = 0 if N == 1 else 2
+    return ymaps * (H + pad) + pad, xmaps * (W + pad) + pad, 3
+
+
+def media_ws_bytes(n_images):
+    """bytes of workspace hd_media_render needs in normalise mode for a batch of `n_images`"""
+    n = int(_abi.load().hd_media_ws_bytes(int(n_images)))
+    if n < 0:
+        raise ValueError("media_render: need 1 <= N <= 16384 images (got %d)" % n_images)
+    return n
+
+
+def _media_check(x, mode, det, gt, nrow):
+    """Shape / dtype checks shared by media_render and media_render_host, from host metadata only.  -> (mode code, P, Q)."""
+    m = MEDIA_MODES.get(mode, mode) if isinstance(mode, str) else mode
+    if m not in (MEDIA_QUANTISE, MEDIA_NORMALISE):
+        raise ValueError("media_render: mode must be 'quantise' or 'normalise' (got %r)" % (mode,))
+    if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32 or min(x.shape) < 1:
+        raise ValueError("media_render: images must be a float32 [N, 3, H, W] batch (got %s %s)" % (x.dtype, tuple(x.shape)))
+    N, _, H, W = x.shape
+    if max(H, W) > MEDIA_MAX_SIDE:
+        raise ValueError("media_render: max(H, W) must be <= %d: the reference's outline thickness becomes 2 from 1500 on and thickness 2 "
+                         "is not built (got %d x %d)" % (MEDIA_MAX_SIDE, H, W))
+    if int(nrow) < 1:
+        raise ValueError("media_render: nrow must be >= 1 (got %r)" % (nrow,))
+    P = Q = 0
+    if m == MEDIA_QUANTISE:
+        if det is not None or gt is not None:
+            raise ValueError("media_render: quantise mode draws no boxes; pass detections / ground truths with mode='normalise'")
+        return m, P, Q
+    if det is not None:
+        b, s, c = det
+        P = int(s.shape[1]) if s.dim() == 2 else -1
+        if tuple(b.shape) != (N, P, 4) or tuple(s.shape) != (N, P) or tuple(c.shape) != (N,):
+            raise ValueError("media_render: detections are (boxes [N, P, 4], scores [N, P], count [N]) (got %s, %s, %s for N = %d)"
+                             % (tuple(b.shape), tuple(s.shape), tuple(c.shape), N))
+        if b.dtype not in (torch.float32, torch.float64) or s.dtype != torch.float32:
+            raise TypeError("media_render: detection boxes must be float32 or float64 and scores float32 (got %s, %s)" % (b.dtype, s.dtype))
+        if P > MEDIA_DET_CAP:
+            raise ValueError("media_render: %d detections per image, the cap is %d" % (P, MEDIA_DET_CAP))
+    if gt is not None:
+        b, c = gt
+        Q = int(b.shape[1]) if b.dim() == 3 else -1
+        if tuple(b.shape) != (N, Q, 4) or tuple(c.shape) != (N,):
+            raise ValueError("media_render: ground truths are (boxes [N, Q, 4], count [N]) (got %s, %s for N = %d)"
+                             % (tuple(b.shape), tuple(c.shape), N))
+        if Q > MEDIA_GT_CAP:
+            raise ValueError("media_render: %d ground truths per image, the cap is %d" % (Q, MEDIA_GT_CAP))
+    return m, P, Q
+
+
+def media_render(x, mode, det=None, gt=None, threshold=0.5, nrow=8, out=None, ws=None):
+    """hd_media_render: a float32 batch [N, 3, H, W] on the GPU (contiguous, or any view with dense planes such as the stride-0 channel
+    view of a one-plane IR batch, read in place) -> ONE uint8 HWC image [CH, CW, 3] holding the batch as make_grid(nrow, padding=2) lays
+    it out (`media_canvas_shape`), ready for PIL.Image.fromarray.
+    mode 'quantise': save_image's trunc(clamp(x*255 + 0.5, 0, 255)), no boxes.  mode 'normalise': per image and channel min-max
+    normalisation, trunc(v*255), then 1-pixel outlines: `gt` = (boxes [N, Q, 4], count [N]) in yellow, then `det` = (boxes [N, P, 4]
+    float32 / float64, scores [N, P] float32, count [N]) with score > float32(threshold) in red (arithmetic: include/hallucidet_hip.h).
+    Image n draws its first count[n] rows.  The filter and the integer conversion run on the device: no host sync, capturable.  P <= 1024,
+    Q <= 512, max(H, W) <= 1499 or it raises, from the shapes.  `ws`: uint8 device tensor of media_ws_bytes(N) bytes kept by a caller on
+    ONE stream (normalise only); allocated per call when None.  -> out (a new tensor unless given)."""
+    m, P, Q = _media_check(x, mode, det, gt, nrow)
+    _need_cuda(x, out, ws, *(det or ()), *(gt or ()))
+    if not dense_planes(x):
+        raise ValueError("media_render: the H x W planes of the batch must be dense (strides %s); see ops.as_dense_planes_f32" % (tuple(x.stride()),))
+    N, _, H, W = x.shape
+    shape = media_canvas_shape(x.shape, nrow)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=x.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError("media_render: out must be a contiguous uint8 tensor of shape %s" % (shape,))
+    db = ds = dc = gb = gc = None
+    if P:
+        db, ds, dc = det[0].contiguous(), det[1].contiguous(), det[2].to(torch.int32).contiguous()
+    if Q:
+        gb, gc = gt[0].to(torch.float64).contiguous(), gt[1].to(torch.int32).contiguous()
+    lib = _abi.load()
+    if m == MEDIA_NORMALISE:
+        need = media_ws_bytes(N)
+        if ws is None:
+            ws = torch.empty((need,), dtype=torch.uint8, device=x.device)
+        elif ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous():
+            raise ValueError("media_render: ws must be a contiguous uint8 tensor of at least %d bytes" % need)
+    check(lib.hd_media_render(ptr(x), x.stride(0), x.stride(1), N, H, W, int(nrow), m, ptr(db), int(P and db.dtype == torch.float64), ptr(ds),
+                              ptr(dc), P, float(threshold), ptr(gb), ptr(gc), Q, ptr(out), ptr(ws), _stream()), "hd_media_render")
+    return out
+
+
+def media_render_host(x, mode, det=None, gt=None, threshold=0.5, nrow=8):
+    """`media_render` for tensors on the CPU: the same arithmetic in numpy, one fp32 operation at a time (the GPU tests hold the kernel
+    and this function to one oracle).  -> uint8 tensor [CH, CW, 3]."""
+    import numpy as np
+    m, P, Q = _media_check(x, mode, det, gt, nrow)
+    if x.is_cuda:
+        raise RuntimeError("media_render_host takes CPU tensors; media_render is the GPU path")
+    N, _, H, W = x.shape
+    CH, CW, _ = media_canvas_shape(x.shape, nrow)
+    xmaps, pad = min(int(nrow), N), (0 if N == 1 else 2)
+    canvas = np.zeros((CH, CW, 3), dtype=np.uint8)
+    f255, half = np.float32(255.0), np.float32(0.5)
+    thr = np.float32(threshold)
+
+    def corners(b):
+        return np.trunc(np.clip(np.nan_to_num(b.detach().numpy().astype(np.float64), nan=-2.0 ** 20), -2.0 ** 20, 2.0 ** 20)).astype(np.int64)
+
+    def outline(img, box, colour):
+        x1, y1, x2, y2 = (int(v) for v in box)
+        xa, xb = max(min(x1, x2), 0), min(max(x1, x2), W - 1)
+        ya, yb = max(min(y1, y2), 0), min(max(y1, y2), H - 1)
+        for yy in (y1, y2):
+            if 0 <= yy < H and xa <= xb:
+                img[yy, xa:xb + 1] = colour
+        for xx in (x1, x2):
+            if 0 <= xx < W and ya <= yb:
+                img[ya:yb + 1, xx] = colour
+
+    for k in range(N):
+        a = x[k].detach().numpy().astype(np.float32, copy=False)
+        if m == MEDIA_QUANTISE:
+            u8 = np.clip(a * f255 + half, np.float32(0.0), f255).astype(np.uint8)
+        else:
+            u8 = np.zeros((3, H, W), dtype=np.uint8)
+            for c in range(3):
+                mn, mx = a[c].min(), a[c].max()
+                rng = np.float32(mx - mn)
+                if rng != 0:
+                    u8[c] = (((a[c] - mn) / rng) * f255).astype(np.uint8)
+        r0, c0 = (k // xmaps) * (H + pad) + pad, (k % xmaps) * (W + pad) + pad
+        cell = canvas[r0:r0 + H, c0:c0 + W]
+        cell[...] = u8.transpose(1, 2, 0)
+        if Q:
+            for box in corners(gt[0][k, :max(0, min(int(gt[1][k]), Q))]):
+                outline(cell, box, (255, 255, 0))
+        if P:
+            n = max(0, min(int(det[2][k]), P))
+            keep = det[1][k, :n].detach().numpy().astype(np.float32, copy=False) > thr
+            for box in corners(det[0][k, :n])[keep]:
+                outline(cell, box, (255, 0, 0))
+    return torch.from_numpy(canvas)
+
+
 # COCO mAP evaluation grid of hd_map_match / hd_map_accumulate (include/hallucidet_hip.h)
 MAP_NUM_IOU, MAP_NUM_AREA, MAP_NUM_MAXDET, MAP_NUM_REC = 10, 4, 3, 101
 MAP_MAX_DET, MAP_DET_CAP, MAP_GT_CAP = 100, 1024, 512

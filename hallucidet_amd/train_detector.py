@@ -26,7 +26,7 @@ from .utils.utils import Utils
 class DetectorLit:
     def __init__(self, batch_size=4, wandb_logger=None, lr=0.0001, detector_name='fasterrcnn', pretrained=True, optimizer_name='adam',
                  modality=None, directly_coco=False, detector=None, device='cuda', loss_scale=1024.0, precision=16, map_device='cpu',
-                 ir_preprocess='none'):
+                 ir_preprocess='none', media=None):
         if not any(k in detector_name for k in ('fasterrcnn', 'retinanet', 'fcos')):
             raise ValueError("unknown detector %r (fasterrcnn / retinanet / fcos)" % (detector_name,))
         self.wandb_logger, self.lr, self.batch_size = wandb_logger, lr, batch_size
@@ -38,6 +38,8 @@ class DetectorLit:
         if ir_preprocess not in IR_PREPROCESS_NAMES:
             raise ValueError("unknown ir_preprocess %r (one of %s)" % (ir_preprocess, ", ".join(IR_PREPROCESS_NAMES)))
         self.ir_preprocess = ir_preprocess
+        self.media = media                    # utils.media.MediaWriter (--save-media) or None: validation / test write `input` and `output_det`
+        self.current_epoch = 0                # set by Trainer before validate / test: names the media files
         self.detector = detector if detector is not None else Detector(name=detector_name, pretrained=pretrained,
                                                                        n_classes=getattr(getattr(Config, 'Dataset', None), 'n_classes', 2), size=Config.Detector.input_size,
                                                                        modality=modality, directly_coco=directly_coco).detector
@@ -128,6 +130,8 @@ class DetectorLit:
             losses_det, detections = Detector.calculate_loss(self.detector, imgs, targets, train_det=False, model_name=self.detector_name)
         self._last_detections = detections
         self._metric('val').update(detections, targets)          # train_detector.py:220
+        if self.media is not None and self.media.wants(batch_idx):
+            self._log_media('val', batch_idx, imgs, detections, targets)
         # train_detector.py:224-229: the validation total is the UNWEIGHTED sum
         if 'fasterrcnn' in self.detector_name:
             return losses_det['loss_box_reg'] + losses_det['loss_classifier'] + losses_det['loss_objectness'] + losses_det['loss_rpn_box_reg']
@@ -139,7 +143,16 @@ class DetectorLit:
             _, detections = Detector.calculate_loss(self.detector, imgs, targets, train_det=False, model_name=self.detector_name)
         self._last_detections = detections
         self._metric('test').update(detections, targets)         # train_detector.py:300
+        if self.media is not None and self.media.wants(batch_idx):
+            self._log_media('test', batch_idx, imgs, detections, targets)
         return detections
+
+    def _log_media(self, split, batch_idx, imgs, detections, targets):
+        """train_detector.py:245, 302: the input batch as save_image quantises it, and min-max normalised with ground truths and
+        detections above the threshold."""
+        imgs = Utils.stack_images(imgs, device=self.dev)
+        self.media.log(split, self.current_epoch, batch_idx, {'input': (imgs, 'quantise', None, None),
+                                                              'output_det': (imgs, 'normalise', detections, targets)})
 
     def _metric(self, split):
         from .metrics import Detection

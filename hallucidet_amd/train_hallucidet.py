@@ -52,7 +52,7 @@ class EncoderDecoderLit(nn.Module):
     def __init__(self, batch_size=4, wandb_logger=None, model_name='resnet34', in_channels=3, output_channels=3, lr=0.0001,
                  loss_pixel=None, loss_perceptual=None, detector_name='fasterrcnn', train_det=False, fuse_data='none',
                  scheduler_on=False, detector=None, precision=16, device='cuda', use_graphs=True, map_device='cpu',
-                 ir_preprocess='none'):
+                 ir_preprocess='none', media=None):
         super().__init__()
         self.model_name, self.wandb_logger = model_name, wandb_logger
         self.in_channels, self.output_channels = in_channels, output_channels
@@ -69,6 +69,10 @@ class EncoderDecoderLit(nn.Module):
         if ir_preprocess not in IR_PREPROCESS_NAMES:
             raise ValueError("unknown ir_preprocess %r (one of %s)" % (ir_preprocess, ", ".join(IR_PREPROCESS_NAMES)))
         self.ir_preprocess = ir_preprocess
+        # utils.media.MediaWriter (--save-media) or None: validation / test write the reference's panels for the batches it selects;
+        # the training step never looks at it
+        self.media = media
+        self.current_epoch = 0                # set by Trainer before validate / test: names the media files
         # src/losses/losses.py through train_hallucidet.py:115-116: 'mse' / 'l1' -> the HIP pixel loss (hd_pixel_loss), anything else
         # None; LPIPS raises (the `lpips` package and its weights are not available), the other perceptual names select nothing
         self.loss_pixel = Reconstruction.select_loss_pixel(loss_pixel=loss_pixel)
@@ -133,6 +137,8 @@ class EncoderDecoderLit(nn.Module):
             imgs_ir_pass = imgs_ir_three_channel
             if self.ir_preprocess != 'none' and step != 'train':
                 imgs_ir_pass = CnnBasedThermalInfraredDA.apply_preset(imgs_ir_three_channel, self.ir_preprocess)
+            if self.media is not None:
+                self._media_ir_pass = imgs_ir_pass          # the batch the IR detector pass reads: the `output_ir_det` panel
             losses_det, loss_det_total, (detections_hall, detections_rgb, detections_ir) = self._detector_section(
                 imgs_hallucinated, imgs_rgb, imgs_ir_pass, targets_rgb, targets_ir, step, train_det)
         total_loss = loss_det_total
@@ -279,7 +285,21 @@ class EncoderDecoderLit(nn.Module):
         m["rgb"].update(d["rgb"], targets_rgb)          # :213-215 / :399-401
         m["hall"].update(d["hall"], targets_ir)
         m["ir"].update(d["ir"], targets_ir)
+        if self.media is not None and self.media.wants(batch_idx):
+            self._log_media(split, batch_idx, out['output'], d, targets_rgb, targets_ir)
         return out['loss']['total'], d
+
+    def _log_media(self, split, batch_idx, o, d, targets_rgb, targets_ir):
+        """The reference's validation / test panels (train_hallucidet.py:309-320, 403-410): raw inputs and output as save_image quantises
+        them, the three detector passes over min-max normalised images with ground truths and detections above the threshold."""
+        self.media.log(split, self.current_epoch, batch_idx, {
+            'input_ir': (o['imgs_ir'], 'quantise', None, None),
+            'input_rgb': (o['imgs_rgb'], 'quantise', None, None),
+            'output_hal': (o['imgs_hallucinated'], 'quantise', None, None),
+            'output_hal_det': (o['imgs_hallucinated'], 'normalise', d['hall'], targets_ir),
+            'output_rgb_det': (o['imgs_rgb'], 'normalise', d['rgb'], targets_rgb),
+            'output_ir_det': (self._media_ir_pass, 'normalise', d['ir'], targets_ir),
+        })
 
     def validation_step(self, val_batch, batch_idx):
         return self._eval_step(val_batch, batch_idx, 'val')

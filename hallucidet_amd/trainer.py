@@ -124,6 +124,7 @@ class Trainer:
     def validate(self, model, loader):
         self._flush_deferred_checks(model)          # the last training batch's degenerate-box flag is read here, not during validation
         state = self._set_eval(model)
+        model.current_epoch = self.current_epoch          # read by the media writer's file names (utils/media.py)
         try:
             tot, n = 0.0, 0
             for i, batch in enumerate(DevicePrefetcher(loader, self.device)):
@@ -185,6 +186,7 @@ class Trainer:
 
     def test(self, model, datamodule):
         state = self._set_eval(model)
+        model.current_epoch = self.current_epoch
         try:
             for i, batch in enumerate(DevicePrefetcher(datamodule.test_dataloader(), self.device)):
                 model.test_step(batch, i)

@@ -1,5 +1,6 @@
 """Hot-path helpers of the reference's `Utils` (src/utils/utils.py:13-53,237-254,333-338): same names and semantics.
-Plotting / VOC-XML helpers of that class are outside the hot path (SURVEY #8)."""
+`plot_each_image` (utils.py:257-297) renders through the media kernel (hd_media_render, utils/media.py); the text labels of `show_bbox`
+and the VOC-XML helpers of that class stay out (SURVEY #8)."""
 import torch
 
 
@@ -76,6 +77,16 @@ class Utils():
         rng = maxs - mins
         images.copy_(torch.where(rng != 0, (images - mins) / torch.where(rng != 0, rng, torch.ones_like(rng)), torch.zeros_like(images)))
         return images
+
+    @staticmethod
+    def plot_each_image(image, output, target, threshold=0.5):
+        """utils.py:257-297 for one image [3, H, W]: per-channel min-max normalisation, trunc(v * 255), the target's boxes in yellow, then
+        the output's boxes with score > threshold in red, 1 pixel wide -> numpy [3, H, W] float64 in [0, 1] (= the uint8 image / 255.0,
+        the reference's return value).  One hd_media_render call for a GPU image (its numpy twin for a CPU image); `image` is not
+        modified.  Not drawn: the text labels and their filled boxes (`show_bbox(..., label=None)`)."""
+        from .media import render_panel
+        canvas = render_panel(image.detach()[None], "normalise", [output], [target], threshold=threshold, nrow=1)
+        return canvas.cpu().numpy().transpose(2, 0, 1) / 255.0
 
     @staticmethod
     def filter_dictionary(input_dict, filter_keys):

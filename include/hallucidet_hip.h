@@ -514,6 +514,37 @@ int hd_augment_u8(const uint8_t* x, const float* params, int N, int C, int H, in
 int64_t hd_ir_preprocess_ws_bytes(int N, int C, int H, int W, int n_stage); /* < 0: bad shape (HD_E_ARG) */
 int hd_ir_preprocess(const float* x, int N, int C, int H, int W, const int* stages, int n_stage, float* out, float* q_out, void* ws,
                      void* stream);
+/* Detection media panels (the reference's Utils.plot_each_image / show_bbox, src/utils/utils.py:137-297, and torchvision's make_grid +
+ * save_image quantisation) as one rendered uint8 image per batch (csrc/media.hip).
+ * x: fp32 [N][3][H][W] with dense planes, image stride stride_n and channel stride stride_c in floats (stride_c = 0: one plane read for
+ * the three channels).  canvas: uint8 HWC [CH][CW][3], every byte written by the call:
+ *   xmaps = min(nrow, N), ymaps = ceil(N / xmaps), pad = 2 (0 when N == 1), CH = ymaps*(H+pad)+pad, CW = xmaps*(W+pad)+pad,
+ *   image k at rows (k / xmaps)*(H+pad)+pad.. and columns (k % xmaps)*(W+pad)+pad.., everything else 0 (make_grid, pad_value 0).
+ * HD_MEDIA_QUANTISE   u8 = trunc(clamp(x*255 + 0.5, 0, 255)): an fp32 product, then an fp32 sum (save_image).  No boxes are drawn
+ *                     and the box arguments are ignored.
+ * HD_MEDIA_NORMALISE  per image and channel mn / mx = the plane's exact fp32 min / max; v = (x - mn) / (mx - mn) (one fp32
+ *                     subtraction, one IEEE division) when mx - mn != 0, else 0; u8 = trunc(v*255).  Finite input only.  Then 1-pixel
+ *                     box outlines, clipped to the image: first the gt_count[n] (clamped to 0..Q) ground truths gt_boxes [N][Q][4]
+ *                     fp64 in (255, 255, 0), then those of the det_count[n] (clamped to 0..P) detections det_boxes [N][P][4] (fp32, or
+ *                     fp64 when det_boxes_f64) whose det_scores [N][P] fp32 are > threshold (fp32, strict) in (255, 0, 0).  Corners
+ *                     (x1, y1, x2, y2) are truncated toward zero; a box paints y in {y1, y2} for min(x1,x2) <= x <= max(x1,x2) and
+ *                     x in {x1, x2} for min(y1,y2) <= y <= max(y1,y2).  P = 0 / Q = 0: the pointers may be NULL.
+ * ws: hd_media_ws_bytes(N) bytes of device memory (NORMALISE only; may be NULL for QUANTISE), contents irrelevant.
+ * NORMALISE = one min/max launch (block partials, combined with integer LDS atomics on the ordered image of the float bits: any order
+ * gives the same bits) + the render launch; QUANTISE = the render launch.  No host synchronisation, capturable, the same bytes from
+ * run to run.  The render stages one canvas row (or a group of its cells) in LDS and stores it in 16-byte pieces; the fp32 loads move
+ * 16 bytes per lane when W % 4 == 0, both strides are multiples of 4 and x is 16-byte aligned, else one float per lane.
+ * Null x / canvas (/ ws, box pointers with P or Q > 0 in NORMALISE), N, H, W or nrow < 1, max(H, W) > HD_MEDIA_MAX_SIDE (thickness 2
+ * is not built), P > HD_MEDIA_DET_CAP, Q > HD_MEDIA_GT_CAP, an unknown mode -> HD_E_ARG. */
+#define HD_MEDIA_QUANTISE 0
+#define HD_MEDIA_NORMALISE 1
+#define HD_MEDIA_MAX_SIDE 1499
+#define HD_MEDIA_DET_CAP 1024
+#define HD_MEDIA_GT_CAP 512
+int64_t hd_media_ws_bytes(int N); /* < 0: bad N (HD_E_ARG) */
+int hd_media_render(const float* x, int64_t stride_n, int64_t stride_c, int N, int H, int W, int nrow, int mode, const void* det_boxes,
+                    int det_boxes_f64, const float* det_scores, const int32_t* det_count, int P, float threshold, const double* gt_boxes,
+                    const int32_t* gt_count, int Q, uint8_t* canvas, void* ws, void* stream);
 /* COCO mAP on the device (hallucidet_amd/metrics/metrics.py `_evaluate_img` / `_accumulate`, restated bit for bit; csrc/coco_map.hip).
  * Fixed evaluation grid: 10 IoU thresholds, 4 area ranges (all, small, medium, large), max-dets 1 / 10 / 100, 101 recall thresholds. */
 #define HD_MAP_NUM_IOU 10

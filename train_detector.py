@@ -35,6 +35,10 @@ def main(argv=None):
     kw = dict(batch_size=args.batch, lr=1e-4 if args.lr is None else args.lr, detector_name=Config.Detector.name, pretrained=args.pretrained,
               modality=args.modality, directly_coco=args.directly_coco, device=dev, precision=args.precision,
               map_device=args.map_device, ir_preprocess=args.ir_preprocess)
+    if args.save_media:
+        from hallucidet_amd.utils.media import MediaWriter
+        kw["media"] = MediaWriter(args.save_media, every=args.media_every, offset=1, threshold=args.threshold, max_batches=args.media_max,
+                                  rank=rank)
     model = DetectorLit.load_from_checkpoint(args.pre_train_path, **kw) if args.pre_train_path else DetectorLit(**kw)
     model.prepare()
     out_dir = os.path.join("lightning_logs", args.wandb_project, args.wandb_name, "_".join([dataset, args.modality, Config.Detector.name]))
@@ -48,6 +52,8 @@ def main(argv=None):
     tr.fit(model, dm)
     if rank == 0:
         print("test:", {k: (v.tolist() if torch.is_tensor(v) else v) for k, v in tr.test(model, dm).items()})
+    if model.media is not None:
+        model.media.close()
     if world > 1:
         torch.distributed.destroy_process_group()
 

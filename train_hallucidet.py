@@ -26,6 +26,15 @@ def print_ap50(maps, ir_preprocess=None):
     print("HalluciDet   on IR  AP@50: ", g("map_hall"))
 
 
+def media_writer(args, rank=0):
+    """--save-media DIR -> the MediaWriter of the three scripts (None when the flag is absent): the reference's cadence (every
+    --media-every batches at phase 1), --threshold for the detections, at most --media-max batches per split and epoch."""
+    if not args.save_media:
+        return None
+    from hallucidet_amd.utils.media import MediaWriter
+    return MediaWriter(args.save_media, every=args.media_every, offset=1, threshold=args.threshold, max_batches=args.media_max, rank=rank)
+
+
 def main(argv=None):
     Config.set_environment()
     args = Config.argument_parser(argv)
@@ -51,7 +60,7 @@ def main(argv=None):
               output_channels=Config.EncoderDecoder.out_channels_decoder, lr=1e-4 if args.lr is None else args.lr,
               detector_name=Config.Detector.name, train_det=Config.Detector.train_det, fuse_data=args.fuse_data, precision=args.precision, device=dev,
               loss_pixel=Config.Losses.pixel, loss_perceptual=Config.Losses.perceptual, map_device=args.map_device,
-              ir_preprocess=args.ir_preprocess)
+              ir_preprocess=args.ir_preprocess, media=media_writer(args, rank))
     model = EncoderDecoderLit.load_from_checkpoint(args.pre_train_path, strict=False, **kw) if args.pre_train_path else EncoderDecoderLit(**kw)
     if args.detector_path:
         from hallucidet_amd.checkpoint import load_detector
@@ -64,6 +73,8 @@ def main(argv=None):
     if rank == 0:
         tr.save_checkpoint(model, os.path.join(out_dir, "encoder_decoder_pl.ckpt"))
         print_ap50(tr.test(model, dm), ir_preprocess=args.ir_preprocess)
+    if model.media is not None:
+        model.media.close()
     if world > 1:
         torch.distributed.destroy_process_group()
 
