@@ -223,44 +223,6 @@ __global__ void bn_bwd_reduce_kernel(const f16* __restrict__ dz, const f16* __re
   }
 }
 
-// column c of the partial rows; the common 16-row case is unrolled so that all 32 loads are in flight at once
-__device__ __forceinline__ void sum_part_rows(const float* __restrict__ part, int rows, int C, int c, float& sg, float& sgx) {
-  if (rows == 16) {
-    float a[16], b[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      a[r] = part[(size_t)r * 2 * C + c];
-      b[r] = part[(size_t)r * 2 * C + C + c];
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      sg += a[r];
-      sgx += b[r];
-    }
-    return;
-  }
-  // any other row count (<= 64): eight rows per trip, all sixteen loads issued before the first add (a plain loop is one
-  // dependent L2 round trip per row in EVERY block's prologue: measured +0.4 ms per training step)
-  int r = 0;
-  for (; r + 8 <= rows; r += 8) {
-    float a[8], b[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      a[q] = part[(size_t)(r + q) * 2 * C + c];
-      b[q] = part[(size_t)(r + q) * 2 * C + C + c];
-    }
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      sg += a[q];
-      sgx += b[q];
-    }
-  }
-  for (; r < rows; ++r) {
-    sg += part[(size_t)r * 2 * C + c];
-    sgx += part[(size_t)r * 2 * C + C + c];
-  }
-}
-
 // Per-channel coefficients of the BN backward, ONCE per unit: sums any number of partial rows (64 row lanes x 4 channels per
 // block, fixed order), writes coef [5][C] = A, B, D (below), forward scale, forward shift, and dgamma / dbeta.  Before, every
 // block of the apply kernel summed the partial rows itself: up to 64 x 2C floats per block, ten times its payload on the small
