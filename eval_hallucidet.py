@@ -24,7 +24,8 @@ def main(argv=None):
     Config.set_loss_weights(args)        # eval_hallucidet.py:39: the test loss (and val_loss) carry the same weighted terms as training
     dev = args.device if args.device not in (None, "gpu") else "cuda"
     dm = MultiModalDataModule(dataset, args.test, args.test, args.test, args.test, batch_size=args.batch, num_workers=args.num_workers,
-                              ext=args.ext or ".jpg", seed=args.seed)
+                              ext=args.ext or ".jpg", seed=args.seed, cache_units=("test",),
+                              **Config.cache_kwargs(args, dev))          # only the test split is read: only its unit is cached
     kw = dict(batch_size=args.batch, model_name=args.decoder_backbone, detector_name=Config.Detector.name, precision=args.precision, device=dev,
               loss_pixel=Config.Losses.pixel, loss_perceptual=Config.Losses.perceptual, map_device=args.map_device,
               ir_preprocess=args.ir_preprocess, media=media_writer(args))

@@ -133,6 +133,11 @@ class Config:
         p.add_argument("--save-media", type=str, default=None, metavar="DIR")
         p.add_argument("--media-every", type=int, default=100, metavar="N")
         p.add_argument("--media-max", type=int, default=None, metavar="K")
+        # 'hbm': decode the train and test datasets once into GPU memory and build every batch there with one gather launch
+        # (dataloader/cache.py); a dataset that does not fit in --cache-budget-gb (10^9 bytes; default: half of the free memory of the
+        # device) or whose images differ in shape stays on the DataLoader.  Default: off
+        p.add_argument("--cache-dataset", type=str, default="none", choices=["none", "hbm"])
+        p.add_argument("--cache-budget-gb", type=float, default=None, metavar="G")
         p.add_argument("--perceptual", type=str, default=None)
         p.add_argument("--weight-perceptual-rgb", type=float, default=0.0)
         p.add_argument("--weight-perceptual-ir", type=float, default=0.0)
@@ -150,6 +155,12 @@ class Config:
         p.add_argument("--encoder-depth", type=int, default=5)
         p.add_argument('--hallucidet-path', type=str)
         return p.parse_args(argv)
+
+    @staticmethod
+    def cache_kwargs(args, device):
+        """The data modules' cache keywords from --cache-dataset / --cache-budget-gb."""
+        budget = None if args.cache_budget_gb is None else int(args.cache_budget_gb * 1e9)
+        return dict(cache=args.cache_dataset, cache_budget_bytes=budget, device=device)
 
     @staticmethod
     def set_loss_weights(args):

@@ -28,6 +28,10 @@ import numpy as np
 import torch
 from PIL import Image
 
+from .. import ops
+from . import cache as hc
+from .cache import CachedLoader, IndexBatch
+
 
 # ------------------------------------------------------------------------------------------------ annotations
 def _annotation_path(filename, dataset):
@@ -228,14 +232,52 @@ def _loader(ds, batch_size, shuffle, num_workers, seed, rank=0, world_size=1):
     return torch.utils.data.DataLoader(ds, **kw)
 
 
+def _caches(cache, units, names, device, num_workers, budget_bytes, rank, log, data_augmentation, fixed_transformations):
+    """cache = 'none': {} ; 'hbm': {unit name: DeviceDatasetCache or None} (dataloader/cache.py), built in the order of `units`; a unit
+    whose name is not in `names` is not built (its loaders stay DataLoaders)."""
+    if cache == 'none':
+        return {}
+    if cache != 'hbm':
+        raise ValueError("cache must be 'none' or 'hbm' (got %r)" % (cache,))
+    hc.check_cacheable(data_augmentation, fixed_transformations)
+    device = hc.cuda_device(device)
+    if log is None:
+        log = print if rank == 0 else (lambda *a: None)
+    unknown = set(names) - {n for n, _ in units}
+    if unknown:
+        raise ValueError("cache_units names %s; the units are %s" % (sorted(unknown), [n for n, _ in units]))
+    units = [(n, ds) for n, ds in units if n in names]
+    return hc.build_units(units, device, num_workers=num_workers, budget_bytes=budget_bytes, log=log)
+
+
+def _unit_loader(cache, indices, ds, batch_size, shuffle, num_workers, seed, rank=0, world_size=1):
+    """The loader of one split: the DataLoader over `ds`, or, when the split's unit is cached, the CachedLoader over the unit's slots
+    `indices` that yields the same batches."""
+    if cache is None:
+        return _loader(ds, batch_size, shuffle, num_workers, seed, rank, world_size)
+    sampler = ShardedBatchSampler(len(indices), batch_size, rank, world_size, True, seed) if shuffle else None
+    return CachedLoader(cache, indices, batch_size, sampler)
+
+
 class SingleModalDataModule:
+    """cache='hbm' (dataloader/cache.py): the train dataset (serving the train and validation subsets) and then the test dataset are
+    decoded once into GPU memory on `device`, within `cache_budget_bytes` (default: half of the free memory); the loaders then yield
+    index batches that DevicePrefetcher gathers on the GPU.  `cache_units` names the units to build (a script that reads one split only
+    builds that one).  `self.caches` maps the built units' names to the cache, or None for a unit that stayed on the DataLoader."""
+
     def __init__(self, dataset, path_images_train, path_images_test, batch_size=4, num_workers=4, ext='.png', seed=123,
-                 split_ratio_train_valid=0.8, modality='rgb', data_augmentation=None, fixed_transformations=None, rank=0, world_size=1):
-        tr = SingleModalDetectionDataset(dataset, path_images_train, modality=modality, transforms=None, ext=ext, train=True)
-        tr, va = split_dataset(tr, split_ratio=split_ratio_train_valid, seed=seed)
-        self._train = _loader(DatasetTransform(tr, data_augmentation, 'single'), batch_size, True, num_workers, seed, rank, world_size)
-        self._valid = _loader(DatasetTransform(va, fixed_transformations, 'single'), batch_size, False, num_workers, seed)
-        self._test = _loader(SingleModalDetectionDataset(dataset, path_images_test, modality=modality, ext=ext, train=False), batch_size, False, num_workers, seed)
+                 split_ratio_train_valid=0.8, modality='rgb', data_augmentation=None, fixed_transformations=None, rank=0, world_size=1,
+                 cache='none', cache_budget_bytes=None, device=None, log=None, cache_units=('train', 'test')):
+        base = SingleModalDetectionDataset(dataset, path_images_train, modality=modality, transforms=None, ext=ext, train=True)
+        te = SingleModalDetectionDataset(dataset, path_images_test, modality=modality, ext=ext, train=False)
+        tr, va = split_dataset(base, split_ratio=split_ratio_train_valid, seed=seed)
+        c = self.caches = _caches(cache, [("train", base), ("test", te)], cache_units, device, num_workers, cache_budget_bytes, rank, log,
+                                  data_augmentation, fixed_transformations)
+        self._train = _unit_loader(c.get("train"), tr.indices, DatasetTransform(tr, data_augmentation, 'single'), batch_size, True, num_workers,
+                                   seed, rank, world_size)
+        self._valid = _unit_loader(c.get("train"), va.indices, DatasetTransform(va, fixed_transformations, 'single'), batch_size, False,
+                                   num_workers, seed)
+        self._test = _unit_loader(c.get("test"), range(len(te)), te, batch_size, False, num_workers, seed)
 
     def train_dataloader(self):
         return self._train
@@ -248,15 +290,21 @@ class SingleModalDataModule:
 
 
 class MultiModalDataModule:
+    """cache='hbm': as SingleModalDataModule, one RGB and one IR arena per unit; with `ablation_flag` validation reads the test unit."""
+
     def __init__(self, dataset, path_images_train_rgb, path_images_train_ir, path_images_test_rgb, path_images_test_ir, batch_size=4,
                  num_workers=4, ext='.png', seed=123, split_ratio_train_valid=0.8, data_augmentation=None, fixed_transformations=None,
-                 ablation_flag=False, rank=0, world_size=1):
-        tr = MultiModalDetectionDataset(dataset, path_images_train_rgb, path_images_train_ir, modality="both", ext=ext, train=True)
-        tr, va = split_dataset(tr, split_ratio=split_ratio_train_valid, seed=seed)
-        self._train = _loader(DatasetTransform(tr, data_augmentation, 'multimodal'), batch_size, True, num_workers, seed, rank, world_size)
-        self._valid = _loader(DatasetTransform(va, fixed_transformations, 'multimodal'), batch_size, False, num_workers, seed)
-        self._test = _loader(MultiModalDetectionDataset(dataset, path_images_test_rgb, path_images_test_ir, modality="both", ext=ext, train=False),
-                             batch_size, False, num_workers, seed)
+                 ablation_flag=False, rank=0, world_size=1, cache='none', cache_budget_bytes=None, device=None, log=None, cache_units=('train', 'test')):
+        base = MultiModalDetectionDataset(dataset, path_images_train_rgb, path_images_train_ir, modality="both", ext=ext, train=True)
+        te = MultiModalDetectionDataset(dataset, path_images_test_rgb, path_images_test_ir, modality="both", ext=ext, train=False)
+        tr, va = split_dataset(base, split_ratio=split_ratio_train_valid, seed=seed)
+        c = self.caches = _caches(cache, [("train", base), ("test", te)], cache_units, device, num_workers, cache_budget_bytes, rank, log,
+                                  data_augmentation, fixed_transformations)
+        self._train = _unit_loader(c.get("train"), tr.indices, DatasetTransform(tr, data_augmentation, 'multimodal'), batch_size, True,
+                                   num_workers, seed, rank, world_size)
+        self._valid = _unit_loader(c.get("train"), va.indices, DatasetTransform(va, fixed_transformations, 'multimodal'), batch_size, False,
+                                   num_workers, seed)
+        self._test = _unit_loader(c.get("test"), range(len(te)), te, batch_size, False, num_workers, seed)
         if ablation_flag:
             self._valid = self._test
 
@@ -277,7 +325,11 @@ class DevicePrefetcher:
 
     Batch i+1 is staged by a helper thread while the main thread issues step i: the uint8 images are stacked straight into one
     of two reusable pinned buffers per image group, copied on a side HIP stream and divided by 255 on the GPU; the per-image target tensors of one key travel as ONE concatenated pinned copy and are split into views on
-    the device (a pageable .to(device) per tensor is a blocking copy each: 64 of them per LLVIP batch)."""
+    the device (a pageable .to(device) per tensor is a blocking copy each: 64 of them per LLVIP batch).
+
+    A `CachedLoader` (dataloader/cache.py, cache='hbm') yields index batches instead: the images are already in HBM, so only the index
+    vector travels through the pinned slots and `ops.batch_gather` builds the same float batch out of the cache's arena with one launch
+    on the side stream (as uint8 when an augmentation follows); the targets travel exactly as above."""
 
     def __init__(self, loader, device="cuda", augment=None):
         """augment: a `ReferenceAugmentation` (dataloader/augment.py) or None.  When given, single-modal batches are augmented as
@@ -325,12 +377,21 @@ class DevicePrefetcher:
                 u8 = torch.stack(seq)
             else:
                 u8 = self._upload(("img", g), seq, True)
+            return finish(g, u8, augment)
+
+        def gathered(g, idx, idx_host, augment=None):
+            """image group g of an IndexBatch (dataloader/cache.py): one gather launch out of the cache's arena on the staging stream"""
+            arena = batch.cache.arenas[g]
+            if augment is None:
+                return ops.batch_gather(arena, idx, "f32_default", idx_host=idx_host)
+            return finish(g, ops.batch_gather(arena, idx, "u8", idx_host=idx_host), augment)
+
+        def finish(g, u8, augment):
             if augment is not None:
                 if u8.dtype != torch.uint8:
                     raise TypeError("DevicePrefetcher: the augmentation takes uint8 images (got %s)" % u8.dtype)
                 rows = augment.params_for(u8.shape[0], self._batch)
                 if u8.is_cuda:
-                    from .. import ops
                     need = ops.augment_ws_bytes(u8.shape)
                     if self._aug_ws is None or self._aug_ws.numel() < need:       # one workspace: every call runs on the staging stream
                         self._aug_ws = torch.empty((need,), dtype=torch.uint8, device=u8.device)
@@ -357,10 +418,21 @@ class DevicePrefetcher:
                     for o, v in zip(out, vals):
                         o[k] = v.to(self.device, non_blocking=True)
             return out
+        multi = "DevicePrefetcher: the augmentation is defined for single-modal (image, target) batches only; the reference's HalluciDet " \
+                "training has none"
+        if isinstance(batch, IndexBatch):
+            if not self.cuda:
+                raise RuntimeError("DevicePrefetcher: an index batch of the HBM dataset cache can only be staged on the GPU")
+            idx_host = torch.tensor(batch.indices, dtype=torch.int64)
+            idx = self._upload(("idx", 0), [idx_host], False)
+            if batch.cache.groups == 2:
+                if self.augment is not None:
+                    raise ValueError(multi)
+                return gathered(0, idx, idx_host), tgts(0, batch.targets[0]), gathered(1, idx, idx_host), tgts(1, batch.targets[1])
+            return gathered(0, idx, idx_host, self.augment), tgts(0, batch.targets[0])
         if len(batch) == 4:
             if self.augment is not None:
-                raise ValueError("DevicePrefetcher: the augmentation is defined for single-modal (image, target) batches only; the "
-                                 "reference's HalluciDet training has none")
+                raise ValueError(multi)
             return imgs(0, batch[0]), tgts(0, batch[1]), imgs(1, batch[2]), tgts(1, batch[3])
         return imgs(0, batch[0], self.augment), tgts(0, batch[1])
 

@@ -1167,6 +1167,67 @@ def augment_u8(u8, params, out=None, ws=None):
     return out
 
 
+GATHER_MODES = {"u8": 0, "f32_default": 1, "f32_ieee": 2}      # HD_GATHER_* modes of hd_batch_gather_u8
+GATHER_MAX_BATCH = 65535                                       # HD_GATHER_MAX_BATCH
+
+
+def check_gather_indices(idx, n_slots):
+    """The host-side validation of `batch_gather`: every value of `idx` (a host tensor or a sequence of ints) lies in [0, n_slots).
+    -> the indices as a contiguous int64 CPU tensor."""
+    host = idx if torch.is_tensor(idx) else torch.as_tensor(list(idx), dtype=torch.int64)
+    if host.is_cuda:
+        raise ValueError("batch_gather: the indices are validated from their HOST copy (got a tensor on %s)" % host.device)
+    if host.dim() != 1 or host.dtype != torch.int64:
+        raise ValueError("batch_gather: idx must be a 1-D int64 vector (got %s %s)" % (host.dtype, tuple(host.shape)))
+    if host.numel() and (int(host.min()) < 0 or int(host.max()) >= n_slots):
+        bad = [int(v) for v in host.tolist() if v < 0 or v >= n_slots]
+        raise IndexError("batch_gather: index %d is outside the arena's %d slots" % (bad[0], n_slots))
+    return host.contiguous()
+
+
+def batch_gather(arena, idx, mode, out=None, idx_host=None, validate=True):
+    """hd_batch_gather_u8: one batch out of an HBM-resident arena of decoded images.  arena: contiguous uint8 [S, C, H, W] on the GPU
+    (it may exceed 2^32 bytes); idx: N slot numbers, duplicates allowed.  mode names what the result equals bit for bit:
+      'u8'           arena[idx]                                              -> uint8   [N, C, H, W]
+      'f32_default'  arena[idx].float().div_(255.0) evaluated on the GPU     -> float32 [N, C, H, W]
+      'f32_ieee'     arena[idx].float().div_(torch.full((), 255.0, device=)) -> float32 [N, C, H, W]
+    idx on the host (tensor or sequence): validated against S, then uploaded.  idx on the device: the caller passes its host copy as
+    `idx_host` for the validation, or `validate=False` when it has validated the values itself.  An index outside [0, S) raises
+    IndexError before anything is launched.  One launch on the current stream, no host synchronisation."""
+    if mode not in GATHER_MODES:
+        raise ValueError("batch_gather: mode must be one of %s (got %r)" % (sorted(GATHER_MODES), mode))
+    if not torch.is_tensor(arena) or arena.dim() != 4 or arena.dtype != torch.uint8 or not arena.is_contiguous() or arena.numel() == 0:
+        raise ValueError("batch_gather: the arena must be a non-empty contiguous uint8 [S, C, H, W] tensor (got %s %s)"
+                         % (getattr(arena, "dtype", type(arena)), tuple(getattr(arena, "shape", ()))))
+    S, Cc, H, W = arena.shape
+    on_device = torch.is_tensor(idx) and idx.is_cuda
+    if on_device:
+        if idx.dim() != 1 or idx.dtype != torch.int64 or not idx.is_contiguous():
+            raise ValueError("batch_gather: idx must be a contiguous 1-D int64 vector (got %s %s)" % (idx.dtype, tuple(idx.shape)))
+        if validate:
+            if idx_host is None:
+                raise ValueError("batch_gather: a device idx needs its host copy (idx_host=) for the validation, or validate=False")
+            if check_gather_indices(idx_host, S).numel() != idx.numel():
+                raise ValueError("batch_gather: idx_host has %d values, idx %d" % (len(idx_host), idx.numel()))
+    else:
+        idx_host = check_gather_indices(idx, S)          # a host idx is always validated: it costs nothing
+    N = int(idx.numel()) if on_device else int(idx_host.numel())
+    if N < 1 or N > GATHER_MAX_BATCH:
+        raise ValueError("batch_gather: need 1 <= N <= %d indices (got %d)" % (GATHER_MAX_BATCH, N))
+    dtype = torch.uint8 if mode == "u8" else torch.float32
+    if out is not None and (not torch.is_tensor(out) or out.dtype != dtype or tuple(out.shape) != (N, Cc, H, W) or not out.is_contiguous()):
+        raise ValueError("batch_gather: out must be a contiguous %s tensor of shape %s" % (dtype, (N, Cc, H, W)))
+    _need_cuda(arena, out)
+    if on_device and idx.device != arena.device or out is not None and out.device != arena.device:
+        raise ValueError("batch_gather: arena, idx and out must live on one device")
+    if not on_device:
+        idx = idx_host.to(arena.device, non_blocking=True)
+    if out is None:
+        out = torch.empty((N, Cc, H, W), dtype=dtype, device=arena.device)
+    check(_abi.load().hd_batch_gather_u8(ptr(arena), S, ptr(idx), N, Cc * H * W, GATHER_MODES[mode], ptr(out), _stream()), "hd_batch_gather_u8")
+    return out
+
+
 IRP_INVERT, IRP_STRETCH, IRP_EQUALIZE, IRP_BLUR = 0, 1, 2, 3     # HD_IRP_* operation codes of hd_ir_preprocess
 IRP_MAX_STAGES = 4
 IRP_MAX_PIXELS = 1 << 24          # largest H*W of hd_ir_preprocess: its quantile ranks are formed in fp32 (HD_IRP_MAX_PIXELS)

@@ -480,6 +480,21 @@ int hd_pixel_loss(const float* hall, const float* rgb, const float* ir, int N, i
 #define HD_AUG_MAX_PIXELS 16843009 /* 255 * H*W < 2^32 */
 int64_t hd_augment_u8_ws_bytes(int N, int C, int H, int W); /* < 0: bad shape (HD_E_ARG) */
 int hd_augment_u8(const uint8_t* x, const float* params, int N, int C, int H, int W, uint8_t* out, void* ws, void* stream);
+/* Batch assembly from an HBM-resident dataset (csrc/batch_gather.hip, dataloader/cache.py): out[n] = f(arena[idx[n]]), n < N.
+ * arena [S][chw] uint8, dense, chw = C*H*W; it may be larger than 2^32 bytes: the slot offset idx[n] * chw is a 64-bit product.
+ * idx [N] int64 on the device, duplicates allowed, 1 <= N <= HD_GATHER_MAX_BATCH.  The CALLER validates 0 <= idx[n] < S on the host
+ * before the call; the kernel writes nothing for a slot outside the arena instead of reading there.  mode names what out must equal:
+ *   HD_GATHER_U8          out [N][chw] uint8 = the bytes;
+ *   HD_GATHER_F32_DEFAULT out [N][chw] fp32  = (float)b * fp32(1/255): ATen's `u8.float().div_(255.0)` on the GPU;
+ *   HD_GATHER_F32_IEEE    out [N][chw] fp32  = (float)b / 255.0f correctly rounded: ATen's `u8.float().div_(tensor(255.0))`.
+ * One launch, no workspace, no host synchronisation, one writer per output element.  chw % 16 == 0 with arena and out 16-byte aligned
+ * moves 16 bytes per lane and store (the float modes load 4 bytes per float4 stored, so that a wave's loads and stores are each one
+ * contiguous run); any other shape is correct but takes the slow path of one byte per lane. */
+#define HD_GATHER_U8 0
+#define HD_GATHER_F32_DEFAULT 1
+#define HD_GATHER_F32_IEEE 2
+#define HD_GATHER_MAX_BATCH 65535
+int hd_batch_gather_u8(const uint8_t* arena, int64_t S, const int64_t* idx, int N, int64_t chw, int mode, void* out, void* stream);
 /* Image-space IR pre-processing baselines of the reference (src/models/cnnBasedThermalInfraredDA.py: invert, histogram stretching,
  * histogram equalization, 3 x 3 Gaussian blur and their chains) on a planar fp32 batch (csrc/ir_preprocess.hip).
  * x, out [N][C][H][W] fp32, C = 3 or 1, N*C <= 65535, H, W >= 2 (reflect padding), H*W <= HD_IRP_MAX_PIXELS (ranks are formed in

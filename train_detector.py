@@ -31,7 +31,7 @@ def main(argv=None):
         os.environ.setdefault("TORCH_NCCL_AVOID_RECORD_STREAMS", "1")
         torch.distributed.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device(dev))
     dm = SingleModalDataModule(dataset, args.train, args.test, batch_size=args.batch, num_workers=args.num_workers, ext=args.ext or ".jpg",
-                               seed=args.seed, rank=rank, world_size=world, modality=args.modality)
+                               seed=args.seed, rank=rank, world_size=world, modality=args.modality, **Config.cache_kwargs(args, dev))
     kw = dict(batch_size=args.batch, lr=1e-4 if args.lr is None else args.lr, detector_name=Config.Detector.name, pretrained=args.pretrained,
               modality=args.modality, directly_coco=args.directly_coco, device=dev, precision=args.precision,
               map_device=args.map_device, ir_preprocess=args.ir_preprocess)
