@@ -64,6 +64,10 @@ int fill_params(const hd_conv_args* a, ConvP& p) {
   int64_t wb = (int64_t)a->Cout * p.Ktot * 2;
   HD_CHECK_ARG(xb < 0xFFFFFFF0ll && x2b < 0xFFFFFFF0ll && wb < 0xFFFFFFF0ll, "hd_conv2d: tensor larger than 4 GiB (buffer addressing)");
   p.xbytes = (unsigned)xb; p.x2bytes = (unsigned)x2b; p.wbytes = (unsigned)wb;
+#ifdef HD_CONV_TRACE
+  p.trace = nullptr;             // (hd_conv2d alone hands the stamp buffer on)
+  p.trace_tid = 0;
+#endif
   return HD_OK;
 }
 
@@ -244,10 +248,17 @@ static int choose_p8(const ConvP& p, bool allow_m160 = true) {
   return best;
 }
 
-struct TileChoice {
-  int bm, bn;
-  bool use64, deep;
-  int p8cfg;             // p8cfg >= 0: the 8-wave input-patch family (conv3x3_w8.hip) with that tile id
+// The routing decision: made once per problem by route(); the entry points ask it, and the capability functions after it, instead of the use_* predicates.
+enum Family { F_SMALL, F_C64, F_STEM, F_C32, F_CAT, F_GEMM8, F_P8, F_M160, F_IGEMM };     // (the ids hd_conv2d_route reports)
+
+struct Route {
+  Family fam;
+  int bm, bn;          // F_IGEMM: the M x N tile
+  bool use64, deep;    // F_IGEMM: 64-deep K tiles; the deep LDS ring
+  int cfg;             // F_P8: tile id 0..7 (hd_conv_launch_p8); F_GEMM8: 128 / 1128
+  int th, tw;          // F_M160: the pixel tile, (4, 40), (8, 40) or (4, 24)
+  bool par;            // F_IGEMM: the four output-parity classes of a stride-2 data gradient, gridDim.y = 4
+  int M;               // the rows the tile was chosen for: p.M, or the largest parity class (ph = pw = 0)
 };
 
 // tuning hook of the 8-wave patch-staged family (tools/tune_w8.py): cfg -1 = cost model, -2 = never, -3 = cost model without the 160-pixel tile
@@ -270,8 +281,9 @@ extern "C" int hd_conv_tune_w8(int cfg, int nslices) {
 //   * any other conv onto > 64 channels whose 64x128 grid cannot give each CU more than one block: 64x64 tiles, deep ring;
 //   * otherwise: the widest N tile that the channel count fills, 64 rows below 512 blocks, 64-deep K where the channel
 //     count allows, deep ring only at <= 1 block per CU.
-static TileChoice choose_tile(const ConvP& p) {
-  TileChoice c;
+// Fills the tile and the family (F_P8 / F_M160 / F_IGEMM) of `c` for the c.M rows one grid covers.
+static void choose_tile(const ConvP& p, Route& c) {
+  const int M = c.M;
   const bool can64_ch = (p.Cin % 64 == 0) && (p.C2 == 0 || (p.C1 % 64 == 0 && p.C2 % 64 == 0));
   static const int small_n = env_int("HD_CONV_SMALLN", 512);
   static const int force_bk = env_int("HD_CONV_BK", 0);
@@ -280,24 +292,17 @@ static TileChoice choose_tile(const ConvP& p) {
   static const int k1_big = env_int("HD_CONV_K1_BIG", 1024), k1_bk64 = env_int("HD_CONV_K1_BK64", 256);     // A/B knobs of the 1x1 rule
   if (!old_rules && p.KH * p.KW == 1 && p.Cout > 64) {
     c.bn = 64;
-    c.bm = ((int64_t)hd_cdiv(p.M, 128) * hd_cdiv(p.Cout, 64) < k1_big) ? 64 : 128;
+    c.bm = ((int64_t)hd_cdiv(M, 128) * hd_cdiv(p.Cout, 64) < k1_big) ? 64 : 128;
     c.use64 = can64_ch && p.Cin >= k1_bk64;
-    c.deep = false;
-  } else if (!old_rules && p.Cout > 64 && (int64_t)hd_cdiv(p.M, 64) * hd_cdiv(p.Cout, 128) <= 256) {
+  } else if (!old_rules && p.Cout > 64 && (int64_t)hd_cdiv(M, 64) * hd_cdiv(p.Cout, 128) <= 256) {
     c.bm = 64;
     c.bn = 64;
     c.use64 = can64_ch;
-    c.deep = true;
   } else {
     c.bn = pick_bn(p.Cout);
-    c.bm = pick_bm(p.M, p.Cout);
-    int64_t blocks = (int64_t)hd_cdiv(p.M, c.bm) * hd_cdiv(p.Cout, c.bn);
-    if (c.bn == 128 && c.bm == 64 && blocks < small_n) {
-      c.bn = 64;
-      blocks = (int64_t)hd_cdiv(p.M, c.bm) * hd_cdiv(p.Cout, c.bn);
-    }
+    c.bm = pick_bm(M, p.Cout);
+    if (c.bn == 128 && c.bm == 64 && (int64_t)hd_cdiv(M, c.bm) * hd_cdiv(p.Cout, c.bn) < small_n) c.bn = 64;
     c.use64 = can64_ch && c.bn > 32;
-    c.deep = blocks <= 256;
   }
   // Round 6: the deep ring everywhere.  Rounds 3-5 chose the stage count per shape from WARM back-to-back timings (deep only at <= 1 block
   // per CU); in STEP ORDER every layer's weights are a first touch from HBM / the Infinity Cache and the extra K tile in flight is worth more
@@ -313,61 +318,191 @@ static TileChoice choose_tile(const ConvP& p) {
   if (g_ov_bk == 64) c.use64 = can64_ch;
   if (force_deep >= 0) c.deep = force_deep != 0;
   if (g_ov_deep >= 0) c.deep = g_ov_deep != 0;
-  c.p8cfg = -1;
-  if (g_w8_cfg >= 10 && g_w8_cfg < 18 && hd_conv_p8_eligible(p) && g_small_ok) c.p8cfg = g_w8_cfg - 10;
-  if (g_w8_cfg >= 18 && hd_conv_m160_eligible(p) && g_small_ok && !(g_w8_cfg == 20 && p.x2)) c.p8cfg = g_w8_cfg - 10;
-  if ((g_w8_cfg == -1 || g_w8_cfg == -3) && g_small_ok && g_ov_bm < 0 && g_ov_bn < 0 && g_ov_bk < 0) c.p8cfg = choose_p8(p, g_w8_cfg == -1);
-  return c;
+  int p8cfg = -1;        // >= 0: the 8-wave input-patch family with that tile id (0..7 conv3x3_w8.hip, 8..10 conv3x3_m160.hip)
+  if (g_w8_cfg >= 10 && g_w8_cfg < 18 && hd_conv_p8_eligible(p) && g_small_ok) p8cfg = g_w8_cfg - 10;
+  if (g_w8_cfg >= 18 && hd_conv_m160_eligible(p) && g_small_ok && !(g_w8_cfg == 20 && p.x2)) p8cfg = g_w8_cfg - 10;
+  if ((g_w8_cfg == -1 || g_w8_cfg == -3) && g_small_ok && g_ov_bm < 0 && g_ov_bn < 0 && g_ov_bk < 0) p8cfg = choose_p8(p, g_w8_cfg == -1);
+  c.fam = p8cfg >= 8 ? F_M160 : p8cfg >= 0 ? F_P8 : F_IGEMM;
+  if (c.fam == F_P8) c.cfg = p8cfg;
+  if (c.fam == F_M160) c.th = p8cfg == 9 ? 8 : 4, c.tw = p8cfg == 10 ? 24 : 40;
 }
 
+// The only caller of the use_* predicates, choose_gemm8 and choose_tile.  Looks at the problem alone (in_scale is not refused here: the
+// launch does that, the queries never did).
+static Route route(const ConvP& p) {
+  Route r = {};
+  r.M = p.M;
+  if (use_small(p)) { r.fam = F_SMALL; return r; }
+  if (use_c64(p)) { r.fam = F_C64; return r; }
+  if (use_stem(p)) { r.fam = F_STEM; return r; }
+  if (use_c32(p)) { r.fam = F_C32; return r; }
+  if (use_cat(p)) { r.fam = F_CAT; return r; }
+  if ((r.cfg = choose_gemm8(p))) { r.fam = F_GEMM8; return r; }
+  // stride-2 data gradients: four output-parity classes, each walking only the taps that meet non-zero input (conv_params.h); tile choice
+  // and grid are for the largest class.  in_dil == 2 makes every 8-wave tile ineligible (hd_conv_p8_eligible, hd_conv_m160_eligible) and
+  // choose_tile sets use64 only where Cin % 64 == 0, i.e. cin8 % 8 == 0: the class form is never refused once `par` holds.
+  static const int par_on = env_int("HD_CONV_PARITY", 1);
+  r.par = par_on && p.in_dil == 2 && !p.stats && p.stride == 1 && (p.cin8 % 4) == 0 && p.out_mode == HD_OUT_NHWC_F16 && g_small_ok && g_w8_cfg < 0;
+  if (r.par) r.M = p.N * ((p.Ho + 1) / 2) * ((p.Wo + 1) / 2);
+  choose_tile(p, r);
+  return r;
+}
+
+// rows of `stats` (BatchNorm partial sums: one per M tile or per persistent block); F_C32 and F_GEMM8 do not take `stats` at all
+static int stats_rows(const ConvP& p, const Route& r) {
+  switch (r.fam) {
+    case F_SMALL: return hd_conv_small_tiles(p);
+    case F_C64: return hd_conv_c64_rows(p);
+    case F_STEM: return hd_conv_stem_rows(p);
+    case F_CAT: return hd_conv_cat128to32_rows(p);
+    case F_P8: return hd_conv_p8_tiles(p, r.cfg);
+    case F_M160: return hd_conv_m160_tiles(p, r.th, r.tw);
+    case F_IGEMM: return hd_cdiv(r.M, r.bm);
+    default: return 0;
+  }
+}
+
+// does the family's epilogue implement hd_conv_args.bs_* ?  (the 8-wave 3x3 families and the 64 -> 64 kernel; the w8 tiles accept in_scale
+// problems, which no kernel combines with the sums)
+static bool implements_bstat(const ConvP& p, const Route& r) {
+  static const int on = env_int("HD_CONV_BSTAT", 1);
+  return on && (r.fam == F_C64 || ((r.fam == F_P8 || r.fam == F_M160) && !p.in_scale));
+}
+
+// does the family implement this problem's out_pool2 (pooled / split output)?
+static bool implements_pool2(const ConvP& p, const Route& r) {
+  if (!p.pool2) return false;
+  switch (r.fam) {
+    case F_SMALL: return hd_conv_small_pool2_ok(p);
+    case F_C32: return true;                             // (its eligibility includes the out_pool2 = 64 / y2 form)
+    case F_P8: return hd_conv_p8_pool2_ok(p);
+    case F_M160: return hd_conv_m160_pool2_ok(p);
+    default: return false;
+  }
+}
+
+// may the problem be one member of the single-grid igemm launch of hd_conv2d_multi?  (single source, no parity classes)
+static bool shares_igemm_multi(const ConvP& p, const Route& r) {
+  return r.fam == F_IGEMM && !r.par && !p.in_scale && !p.x2 && p.in_dil == 1 && !p.bs_y && !p.pool2;
+}
+
+// may it be one member of the 96-pixel-tile multi launch?
+static bool shares_m96_multi(const ConvP& p, const Route& r) { return r.fam == F_M160 && r.tw == 24 && !p.pool2 && !p.x2; }
+
+// may its grid carry the 8-wave weight gradient of the same layer?  (the 160- / 320- / 96-pixel tiles have no fused weight-gradient grid)
+static bool carries_wgrad(const ConvP& p, const Route& r) {
+  return r.fam == F_P8 && !p.in_scale && !p.x2 && (!p.stats || p.bs_y) && p.in_dil == 1;
+}
+
+// thread blocks of the launch (hd_conv2d_route; each launcher computes its own grid)
+static int grid_blocks(const ConvP& p, const Route& r) {
+  switch (r.fam) {
+    case F_SMALL: return hd_conv_small_tiles(p) < 1536 ? hd_conv_small_tiles(p) : 1536;
+    case F_C64: return hd_conv_c64_rows(p);
+    case F_STEM: return hd_conv_stem_rows(p);
+    case F_C32: { const int t = p.N * hd_cdiv(p.Ho, 8) * hd_cdiv(p.Wo, 16); return t < 256 ? t : 256; }      // 8 x 16-pixel tiles, persistent blocks
+    case F_CAT: return hd_conv_cat128to32_rows(p);
+    case F_GEMM8: return hd_cdiv(p.M, r.cfg == 1128 ? 128 : 256) * hd_cdiv(p.Cout, 128);
+    case F_P8: return hd_conv_p8_tiles(p, r.cfg) * hd_cdiv(p.Cout, (r.cfg & 2) ? 64 : 128);
+    case F_M160: return hd_conv_m160_tiles(p, r.th, r.tw) * hd_cdiv(p.Cout, 64);
+    default: return hd_cdiv(r.M, r.bm) * hd_cdiv(p.Cout, r.bn) * (r.par ? 4 : 1);
+  }
+}
+
+// the single switch over the launchers; `wa`: the weight gradient that shares a F_P8 grid (carries_wgrad)
+static void launch(ConvP& p, const Route& r, hipStream_t s, const hd_wgrad_args* wa = nullptr) {
+  static const int w8_prio = env_int("HD_W8_PRIO", 0);
+  if (r.fam >= F_P8) p.prio = w8_prio;
+  p.M = r.M, p.par = r.par;      // the launchers add gridDim.y = 4
+  switch (r.fam) {
+    case F_SMALL: hd_conv_launch_small(p, s); break;
+    case F_C64: hd_conv_launch_c64(p, s); break;
+    case F_STEM: hd_conv_launch_stem(p, s); break;
+    case F_C32: hd_conv_launch_c32to128(p, s); break;
+    case F_CAT: hd_conv_launch_cat128to32(p, s); break;
+    case F_GEMM8: hd_gemm_w8_launch(p, r.cfg, s); break;
+    case F_P8: if (wa) hd_conv_launch_p8_wgrad(p, r.cfg, wa, s); else hd_conv_launch_p8(p, r.cfg, s); break;
+    case F_M160: hd_conv_launch_m160(p, r.th, r.tw, s); break;
+    case F_IGEMM: if (r.use64) hd_conv_launch_bk64(p, r.bm, r.bn, r.deep, s); else hd_conv_launch_bk32(p, r.bm, r.bn, r.deep, s); break;
+  }
+}
+
+// The queries answer for the problem as it will be launched: with the slab the caller is about to allocate, and for hd_conv2d_bstat_ok with
+// the bs_* request it is about to make (stand-in pointers; routing never dereferences them).  So hd_conv2d_stats_rows does not depend on
+// whether `stats` is set, hd_conv2d_bstat_ok not on the bs_* fields.
+static float g_slab_to_be;
+
+// (the stand-in goes into the argument block: bs_* may then be filled before the slab exists, as fill_params wants `stats` beside them)
 extern "C" int hd_conv2d_stats_rows(const hd_conv_args* a) {
   if (!a) return HD_E_ARG;
+  hd_conv_args b = *a;
+  if (!b.stats) b.stats = &g_slab_to_be;
   ConvP p;
-  int rc = fill_params(a, p);
+  int rc = fill_params(&b, p);
   if (rc) return rc;
-  if (use_small(p)) return hd_conv_small_tiles(p);
-  if (use_c64(p)) return hd_conv_c64_rows(p);
-  if (use_stem(p)) return hd_conv_stem_rows(p);
-  if (use_cat(p)) return hd_conv_cat128to32_rows(p);
-  const TileChoice c = choose_tile(p);
-  if (c.p8cfg >= 8) return hd_conv_m160_tiles(p, c.p8cfg == 9 ? 8 : 4, c.p8cfg == 10 ? 24 : 40);
-  if (c.p8cfg >= 0) return hd_conv_p8_tiles(p, c.p8cfg);
-  return hd_cdiv(p.M, c.bm);
+  return stats_rows(p, route(p));
 }
 
-extern "C" int hd_wgrad(const hd_wgrad_args* a, void* stream);
-extern "C" int hd_conv2d(const hd_conv_args* a, void* stream);
-
-// does this problem run in a kernel whose epilogue implements hd_conv_args.bs_* ?  (the 8-wave patch-staged 3x3 family)
-static bool bstat_kernel(const ConvP& p) {
-  static const int on = env_int("HD_CONV_BSTAT", 1);
-  if (!on || use_small(p) || p.in_scale || p.in_dil != 1 || p.out_mode != HD_OUT_NHWC_F16) return false;
-  if (use_c64(p)) return true;                         // the register-resident 64 -> 64 kernel implements them too
-  return choose_tile(p).p8cfg >= 0;
-}
-
-// is this problem (out_pool2 set) routed to a kernel that implements the pooled / split output?
-static bool pool2_kernel(const ConvP& p) {
-  if (!p.pool2) return false;
-  if (use_small(p)) return hd_conv_small_pool2_ok(p);
-  if (use_c64(p) || use_stem(p)) return false;
-  if (use_c32(p)) return true;                         // (its eligibility includes the out_pool2 = 64 / y2 form)
-  if (use_cat(p) || choose_gemm8(p)) return false;
-  const int cfg = choose_tile(p).p8cfg;
-  return cfg >= 8 ? hd_conv_m160_pool2_ok(p) : (cfg >= 0 && hd_conv_p8_pool2_ok(p));
-}
-
-// does hd_conv2d implement out_pool2 for this problem?
 extern "C" int hd_conv2d_pool2_ok(const hd_conv_args* a) {
   ConvP p;
   if (!a || fill_params(a, p)) return 0;
-  return pool2_kernel(p) ? 1 : 0;
+  return implements_pool2(p, route(p)) ? 1 : 0;
 }
 
 extern "C" int hd_conv2d_bstat_ok(const hd_conv_args* a) {
   ConvP p;
   if (fill_params(a, p)) return 0;
-  return bstat_kernel(p) ? 1 : 0;
+  if (!p.stats) p.stats = &g_slab_to_be;
+  if (!p.bs_y) p.bs_y = (const f16*)p.y;
+  return implements_bstat(p, route(p)) ? 1 : 0;
+}
+
+// what hd_conv2d refuses once the route is known
+static int accepts(const ConvP& p, const Route& r) {
+  HD_CHECK_ARG(!p.bs_y || implements_bstat(p, r), "hd_conv2d: bs_* (BatchNorm backward sums) are implemented by the 8-wave and the 64-channel 3x3 kernels only; "
+                                                  "ask hd_conv2d_bstat_ok first");
+  HD_CHECK_ARG(!p.pool2 || implements_pool2(p, r),
+               "hd_conv2d: out_pool2 is implemented by the small-channel 3x3 kernel (all channels pooled), the 32 -> 128 channel kernel "
+               "(64 pooled channels + y2) and the 8-wave 3x3 family (pooled channels a multiple of 128); ask hd_conv2d_pool2_ok first");
+  HD_CHECK_ARG(!p.in_scale || r.fam == F_SMALL, "hd_conv2d: consumer-side BatchNorm (in_scale / in_shift) is implemented by the small-channel 3x3 kernel only "
+                                                "(3x3 / stride 1 / pad 1, one source, C1 in {8,16,32}, Cout in {16,32} or a <= 16-channel fp32 head)");
+  return HD_OK;
+}
+
+// which kernel would hd_conv2d launch?  (include/hallucidet_hip.h has the layout of `out`)
+extern "C" int hd_conv2d_route(const hd_conv_args* a, int32_t out[8]) {
+  HD_CHECK_ARG(a && out, "hd_conv2d_route: null pointer");
+  ConvP p;
+  int rc = fill_params(a, p);
+  if (rc) return rc;
+  const Route r = route(p);
+  rc = accepts(p, r);
+  if (rc) return rc;
+  out[0] = r.fam == F_IGEMM && r.use64 ? F_IGEMM + 1 : r.fam;
+  out[1] = r.fam == F_IGEMM ? r.bm : r.fam == F_M160 ? r.th : r.cfg;
+  out[2] = r.fam == F_IGEMM ? r.bn : r.tw;
+  out[3] = r.fam == F_IGEMM && r.deep;
+  out[4] = r.par;
+  out[5] = r.M;
+  out[6] = hd_conv2d_stats_rows(a);
+  out[7] = grid_blocks(p, r);
+  return HD_OK;
+}
+
+extern "C" int hd_conv2d(const hd_conv_args* a, void* stream) {
+  ConvP p;
+  int rc = fill_params(a, p);
+  if (rc) return rc;
+#ifdef HD_CONV_TRACE
+  p.trace = g_trace;
+  p.trace_tid = env_int("HD_TRACE_TID", 0);
+#endif
+  const Route r = route(p);
+  rc = accepts(p, r);
+  if (rc) return rc;
+  launch(p, r, (hipStream_t)stream);
+  HD_CHECK_LAUNCH();
+  return HD_OK;
 }
 
 // Data gradient + weight gradient of one layer (both read the same dY): ONE grid when the convolution runs in the 8-wave
@@ -379,20 +514,12 @@ extern "C" int hd_conv2d_wgrad(const hd_conv_args* a, const hd_wgrad_args* wa, v
   ConvP p;
   int rc = fill_params(a, p);
   if (rc) return rc;
-  HD_CHECK_ARG(!p.pool2 || pool2_kernel(p), "hd_conv2d_wgrad: out_pool2 is not implemented for this problem; ask hd_conv2d_pool2_ok first");
-  if (fuse_on && !use_small(p) && !use_c64(p) && !use_stem(p) && !p.in_scale && !p.x2 && (!p.stats || p.bs_y) && p.in_dil == 1 && hd_wgrad_takes_w8(wa)) {
-    const TileChoice c = choose_tile(p);
-    if (c.p8cfg >= 0 && c.p8cfg < 8) {             // (the 160- / 320-pixel tiles have no fused weight-gradient grid: two launches below)
-      static const int w8_prio = env_int("HD_W8_PRIO", 0);
-      p.prio = w8_prio;
-#ifdef HD_CONV_TRACE
-      p.trace = nullptr;
-      p.trace_tid = 0;
-#endif
-      hd_conv_launch_p8_wgrad(p, c.p8cfg, wa, (hipStream_t)stream);
-      HD_CHECK_LAUNCH();
-      return HD_OK;
-    }
+  const Route r = route(p);
+  HD_CHECK_ARG(!p.pool2 || implements_pool2(p, r), "hd_conv2d_wgrad: out_pool2 is not implemented for this problem; ask hd_conv2d_pool2_ok first");
+  if (fuse_on && carries_wgrad(p, r) && hd_wgrad_takes_w8(wa)) {
+    launch(p, r, (hipStream_t)stream, wa);
+    HD_CHECK_LAUNCH();
+    return HD_OK;
   }
   rc = hd_conv2d(a, stream);
   if (rc) return rc;
@@ -400,142 +527,51 @@ extern "C" int hd_conv2d_wgrad(const hd_conv_args* a, const hd_wgrad_args* wa, v
 }
 
 // n independent convolutions in ONE grid when they all resolve to the same 4-wave igemm variant (single source, no parity classes,
-// none of them claimed by the small-channel or the 8-wave kernels); otherwise n hd_conv2d calls.  The tile of the FIRST problem
-// (callers put the largest first) serves all of them: in this family the tile shape does not change a single output bit.
-// HD_CONV_MULTI=0: always separate launches (A/B).
+// none of them claimed by the small-channel or the 8-wave kernels).  The tile of the FIRST problem (callers put the largest first)
+// serves all of them: in this family the tile shape does not change a single output bit.  Otherwise the members the tile model sends
+// to the 96-pixel tile (conv3x3_m160.hip, cfg 10: the small pyramid levels) still share ONE grid -- the same blocks their own launches
+// would run, bit for bit -- and the others are launched one by one.  HD_CONV_MULTI=0: always separate launches, HD_CONV_M96_MULTI=0:
+// no 96-pixel grid (A/B).
 extern "C" int hd_conv2d_multi(const hd_conv_args* args, int n, void* stream) {
   static const int multi_on = env_int("HD_CONV_MULTI", 1);
+  static const int m96_multi_on = env_int("HD_CONV_M96_MULTI", 1);
   HD_CHECK_ARG(args && n >= 1, "hd_conv2d_multi: bad args");
-  bool ok = multi_on && n >= 2 && n <= HD_CONV_MULTI_MAX && g_small_ok && g_w8_cfg < 0;
   static ConvMulti mp;          // 3.3 KB: not on the stack of a ctypes call; the boundary is not re-entrant (SURVEY 8b "Threading")
-  TileChoice c0 = {};
-  for (int i = 0; ok && i < n; ++i) {
-    ConvP& p = mp.p[i];
-    int rc = fill_params(&args[i], p);
-    if (rc) return rc;
-    if (use_small(p) || use_c64(p) || use_stem(p) || use_c32(p) || p.in_scale || p.x2 || p.in_dil != 1 || p.bs_y || p.pool2 || choose_gemm8(p)) { ok = false; break; }
-    const TileChoice c = choose_tile(p);
-    if (c.p8cfg >= 0) { ok = false; break; }
-    if (i == 0) c0 = c;
-    else if (c.use64 != c0.use64) { ok = false; break; }
-#ifdef HD_CONV_TRACE
-    p.trace = nullptr;
-    p.trace_tid = 0;
-#endif
-  }
-  if (ok) {
+  bool taken[HD_CONV_MULTI_MAX] = {};
+  int n96 = 0;                  // members of the 96-pixel grid (launched from two up)
+  if (multi_on && n >= 2 && n <= HD_CONV_MULTI_MAX && g_small_ok && g_w8_cfg < 0) {
+    Route rt[HD_CONV_MULTI_MAX];
+    bool igemm = true;
+    for (int i = 0; i < n; ++i) {
+      int rc = fill_params(&args[i], mp.p[i]);
+      if (rc) return rc;
+      rt[i] = route(mp.p[i]);
+      igemm = igemm && shares_igemm_multi(mp.p[i], rt[i]) && rt[i].use64 == rt[0].use64;
+    }
     mp.n = n;
-    const bool launched = c0.use64 ? hd_conv_launch_bk64_multi(mp, c0.bm, c0.bn, c0.deep, (hipStream_t)stream)
-                                   : hd_conv_launch_bk32_multi(mp, c0.bm, c0.bn, c0.deep, (hipStream_t)stream);
-    if (launched) {
+    if (igemm && (rt[0].use64 ? hd_conv_launch_bk64_multi(mp, rt[0].bm, rt[0].bn, rt[0].deep, (hipStream_t)stream)
+                              : hd_conv_launch_bk32_multi(mp, rt[0].bm, rt[0].bn, rt[0].deep, (hipStream_t)stream))) {
       HD_CHECK_LAUNCH();
       return HD_OK;
     }
-  }
-  // Not one igemm grid: the members the tile model sends to the 96-pixel tile (conv3x3_m160.hip, cfg 10: the small pyramid levels) still share
-  // ONE grid -- the same blocks their own launches would run, bit for bit -- the others are launched one by one.  HD_CONV_M96_MULTI=0: off (A/B).
-  static const int m96_multi_on = env_int("HD_CONV_M96_MULTI", 1);
-  bool taken[HD_CONV_MULTI_MAX] = {};
-  if (multi_on && m96_multi_on && n >= 2 && n <= HD_CONV_MULTI_MAX && g_small_ok && g_w8_cfg < 0) {
-    static ConvMulti m96;
-    m96.n = 0;
-    for (int i = 0; i < n; ++i) {
-      ConvP& p = m96.p[m96.n];
-      int rc = fill_params(&args[i], p);
-      if (rc) return rc;
-      if (use_small(p) || use_c64(p) || use_stem(p) || use_c32(p) || use_cat(p) || choose_gemm8(p) || p.pool2 || p.x2) continue;
-      if (choose_tile(p).p8cfg != 10) continue;
-      HD_CHECK_ARG(!p.bs_y || bstat_kernel(p), "hd_conv2d_multi: bs_* on a problem whose kernel does not implement them");
-#ifdef HD_CONV_TRACE
-      p.trace = nullptr;
-      p.trace_tid = 0;
-#endif
+    // (no member of an all-igemm group is a 96-pixel one: nothing a refused launch touched is used below)
+    for (int i = 0; m96_multi_on && i < n; ++i) {
+      if (!shares_m96_multi(mp.p[i], rt[i])) continue;
+      HD_CHECK_ARG(!mp.p[i].bs_y || implements_bstat(mp.p[i], rt[i]), "hd_conv2d_multi: bs_* on a problem whose kernel does not implement them");
       taken[i] = true;
-      ++m96.n;
+      if (n96 != i) mp.p[n96] = mp.p[i];
+      ++n96;
     }
-    if (m96.n >= 2) {
-      hd_conv_launch_m96_multi(m96, (hipStream_t)stream);
+    if (n96 >= 2) {
+      mp.n = n96;
+      hd_conv_launch_m96_multi(mp, (hipStream_t)stream);
       HD_CHECK_LAUNCH();
-    } else {
-      for (int i = 0; i < n; ++i) taken[i] = false;
     }
   }
   for (int i = 0; i < n; ++i) {
-    if (taken[i]) continue;
+    if (taken[i] && n96 >= 2) continue;
     int rc = hd_conv2d(&args[i], stream);
     if (rc) return rc;
   }
-  return HD_OK;
-}
-
-extern "C" int hd_conv2d(const hd_conv_args* a, void* stream) {
-  ConvP p;
-  int rc = fill_params(a, p);
-  if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-#ifdef HD_CONV_TRACE
-  p.trace = g_trace;
-  p.trace_tid = env_int("HD_TRACE_TID", 0);
-#endif
-  HD_CHECK_ARG(!p.bs_y || bstat_kernel(p), "hd_conv2d: bs_* (BatchNorm backward sums) are implemented by the 8-wave and the 64-channel 3x3 kernels only; "
-                                           "ask hd_conv2d_bstat_ok first");
-  HD_CHECK_ARG(!p.pool2 || pool2_kernel(p),
-               "hd_conv2d: out_pool2 is implemented by the small-channel 3x3 kernel (all channels pooled), the 32 -> 128 channel kernel "
-               "(64 pooled channels + y2) and the 8-wave 3x3 family (pooled channels a multiple of 128); ask hd_conv2d_pool2_ok first");
-  if (use_small(p)) {
-    hd_conv_launch_small(p, s);
-    HD_CHECK_LAUNCH();
-    return HD_OK;
-  }
-  if (use_c64(p)) {
-    hd_conv_launch_c64(p, s);
-    HD_CHECK_LAUNCH();
-    return HD_OK;
-  }
-  if (use_stem(p)) {
-    hd_conv_launch_stem(p, s);
-    HD_CHECK_LAUNCH();
-    return HD_OK;
-  }
-  if (use_c32(p)) {
-    hd_conv_launch_c32to128(p, s);
-    HD_CHECK_LAUNCH();
-    return HD_OK;
-  }
-  if (use_cat(p)) {
-    hd_conv_launch_cat128to32(p, s);
-    HD_CHECK_LAUNCH();
-    return HD_OK;
-  }
-  if (const int g8 = choose_gemm8(p)) {
-    hd_gemm_w8_launch(p, g8, s);
-    HD_CHECK_LAUNCH();
-    return HD_OK;
-  }
-  HD_CHECK_ARG(!p.in_scale, "hd_conv2d: consumer-side BatchNorm (in_scale / in_shift) is implemented by the small-channel 3x3 kernel only "
-                            "(3x3 / stride 1 / pad 1, one source, C1 in {8,16,32}, Cout in {16,32} or a <= 16-channel fp32 head)");
-  // stride-2 data gradients: four output-parity classes, each walking only the taps that meet non-zero input (conv_params.h)
-  static const int par_on = env_int("HD_CONV_PARITY", 1);
-  const bool par = par_on && p.in_dil == 2 && !p.stats && p.stride == 1 && (p.cin8 % 4) == 0 && p.out_mode == HD_OUT_NHWC_F16 && g_small_ok &&
-                   g_w8_cfg < 0;
-  const int M_full = p.M;
-  if (par) p.M = p.N * ((p.Ho + 1) / 2) * ((p.Wo + 1) / 2);      // tile choice / grid for the largest class (ph = pw = 0)
-  const TileChoice c = choose_tile(p);
-  static const int w8_prio = env_int("HD_W8_PRIO", 0);
-  p.prio = w8_prio;
-  const int bm = c.bm, bn = c.bn;
-  const bool use64 = c.use64, deep = c.deep;
-  if (par && c.p8cfg < 0 && (c.use64 ? (p.cin8 % 8) == 0 : true)) {
-    p.par = 1;                     // the launchers add gridDim.y = 4
-  } else {
-    p.M = M_full;
-  }
-  if (c.p8cfg >= 8) {
-    hd_conv_launch_m160(p, c.p8cfg == 9 ? 8 : 4, c.p8cfg == 10 ? 24 : 40, s);
-  } else if (c.p8cfg >= 0) {
-    hd_conv_launch_p8(p, c.p8cfg, s);
-  } else if (use64) hd_conv_launch_bk64(p, bm, bn, deep, s);
-  else hd_conv_launch_bk32(p, bm, bn, deep, s);
-  HD_CHECK_LAUNCH();
   return HD_OK;
 }

@@ -131,14 +131,15 @@ def conv2d(x, w, KH, KW, *, x2=None, bias=None, res=None, mask=None, stride=1, p
     if bstat is not None:
         bstat["part"] = None
         if x.dtype == torch.float16 and not want_stats and lib.hd_conv2d_bstat_ok(C.byref(a)) == 1:
-            rows = lib.hd_conv2d_stats_rows(C.byref(a))
-            check(0 if rows > 0 else rows, "hd_conv2d_stats_rows")
-            part = torch.empty((rows, 2 * Cout), dtype=torch.float32, device=x.device)
             by, bz = bstat["y"], bstat.get("z")
             assert by.shape == y.shape and by.dtype == y.dtype and by.is_contiguous() and (bz is None or (bz.shape == y.shape and bz.is_contiguous()))
-            a.stats, a.bs_y, a.bs_z = ptr(part), ptr(by), ptr(bz)
+            a.bs_y, a.bs_z = ptr(by), ptr(bz)
             a.bs_mean, a.bs_invstd, a.bs_gamma, a.bs_beta = ptr(bstat["mean"]), ptr(bstat["invstd"]), ptr(bstat.get("gamma")), ptr(bstat.get("beta"))
             a.bs_relu = 1 if bstat.get("relu", True) else 0
+            rows = lib.hd_conv2d_stats_rows(C.byref(a))         # asked with bs_* filled: the answer is for the block as launched
+            check(0 if rows > 0 else rows, "hd_conv2d_stats_rows")
+            part = torch.empty((rows, 2 * Cout), dtype=torch.float32, device=x.device)
+            a.stats = ptr(part)
             bstat["part"] = part
     if want_stats:
         rows = _abi.fn("hd_conv2d_stats_rows", x)(C.byref(a))

@@ -120,8 +120,23 @@ int hd_conv2d(const hd_conv_args* a, void* stream);
 int hd_conv2d_bstat_ok(const hd_conv_args* a);
 /* 1 if hd_conv2d implements out_pool2 for this problem, else 0 */
 int hd_conv2d_pool2_ok(const hd_conv_args* a);
-/* number of M tiles (rows of `stats`) hd_conv2d will use for this problem */
+/* number of M tiles (rows of `stats`) hd_conv2d will use for this problem.  Contract: the answer is for the argument block AS IT WILL BE
+ * LAUNCHED.  It does not depend on whether `stats` is set (the caller asks before the slab exists), but it does depend on bs_y: a
+ * kernel that does not implement the bs_* sums is not chosen when they are requested, so fill bs_* before asking. */
 int hd_conv2d_stats_rows(const hd_conv_args* a);
+/* Read-only: which kernel hd_conv2d would launch for this argument block (the same routing decision, no launch, no HIP call).
+ *   out[0] family: 0 small-channel 3x3, 1 64 -> 64, 2 stem, 3 32 -> 128, 4 cat 128 -> 32, 5 large-tile GEMM, 6 8-wave patch family,
+ *          7 its 160- / 320- / 96-pixel tiles, 8 4-wave implicit GEMM with 32-deep K tiles, 9 the same with 64-deep K tiles
+ *   out[1], out[2]: families 8 / 9: the M x N tile (bm, bn); 7: the pixel tile (th, tw); 6: the tile id 0..7, 0; 5: the tile (128 / 1128), 0;
+ *          others 0, 0
+ *   out[3] families 8 / 9: 1 = the deep (3-stage) ring; others 0
+ *   out[4] 1 = the four output-parity classes of a stride-2 data gradient share the grid (gridDim.y = 4)
+ *   out[5] M the tile was chosen for (N * Ho * Wo, or the largest parity class)
+ *   out[6] rows of `stats`: what hd_conv2d_stats_rows answers, i.e. of the launch WITH `stats` given (families 3 and 5 and the parity form
+ *          do not take `stats`: such a problem then runs elsewhere and out[6] is that kernel's count)
+ *   out[7] thread blocks of the grid (all four parity classes counted)
+ * Returns HD_OK, or HD_E_ARG for an argument block hd_conv2d would refuse. */
+int hd_conv2d_route(const hd_conv_args* a, int32_t out[8]);
 /* Data gradient of a 7x7 / stride-2 / pad-3 convolution with 64 output and <= 4 input channels (torchvision ResNet.conv1 [EXT] of the
  * frozen detector: the last step of the gradient that trains the hallucination network, src/models/detector.py:24-141) in sub-pixel
  * form: the four output pixels (2I + a, 2J + b) of a low-resolution position are one GEMM row block over the 4 x 4 window

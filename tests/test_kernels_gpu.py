@@ -1996,3 +1996,100 @@ def test_conv_upsample_concat_128_to_32_register_resident_kernel(dev, shape):
     got2, stats2 = ops.conv2d(a, w, 3, 3, x2=skip, up1=True, pad=1, want_stats=True)
     assert torch.equal(got, got2) and torch.equal(stats, stats2)
     assert torch.equal(ops.conv2d(a[:1].contiguous(), w, 3, 3, x2=skip[:1].contiguous(), up1=True, pad=1)[0], got[0])
+
+
+def _conv_args(x, w, y, *, x2=None, K=3, stride=1, pad=1, up1=False, stats=None):
+    """a raw hd_conv_args block (no ops.conv2d in between) and its route"""
+    import ctypes as C
+    from hallucidet_amd import ops, _abi
+    N, Hs, Ws, C1 = x.shape
+    Hin, Win = (2 * Hs, 2 * Ws) if up1 else (Hs, Ws)
+    a = _abi.ConvArgs(x=ops.ptr(x), x2=ops.ptr(x2), w=ops.ptr(w), y=ops.ptr(y), stats=ops.ptr(stats), N=N, Hsrc=Hs, Wsrc=Ws, Hin=Hin, Win=Win, C1=C1,
+                      C2=0 if x2 is None else x2.shape[3], Ho=y.shape[1], Wo=y.shape[2], Cout=y.shape[3], KH=K, KW=K, stride=stride, pad=pad,
+                      up1=int(up1), in_dil=1, act=0, out_mode=0)
+    route = (C.c_int32 * 8)()
+    ops.check(_abi.load().hd_conv2d_route(C.byref(a), route), "hd_conv2d_route")
+    return a, list(route)
+
+
+# (family id of hd_conv2d_route, hd_conv_tune_w8 setting, N, H, W of x, C1, C2, Cout, K, stride, pad, up1); cfg 64: the 64-deep K tiles forced
+# through hd_conv_tune_override (the shipped 1x1 rule takes them from 256 input channels up)
+ROWS_CASES = [(0, -1, 1, 8, 8, 16, 0, 16, 3, 1, 1, False), (1, -1, 1, 8, 16, 64, 0, 64, 3, 1, 1, False), (2, -1, 1, 32, 32, 8, 0, 64, 7, 2, 3, False),
+              (4, -1, 1, 3, 8, 64, 64, 32, 3, 1, 1, True)] + [(6, cfg, 1, 10, 44, 64, 0, 128, 3, 1, 1, False) for cfg in (10, 11, 12, 13)] + \
+             [(7, cfg, 1, 10, 44, 64, 0, 128, 3, 1, 1, False) for cfg in (18, 19, 20)] + \
+             [(8, -1, 1, 9, 9, 24, 0, 40, 3, 1, 1, False), (9, 64, 1, 9, 9, 64, 0, 72, 1, 1, 0, False)]
+
+
+@pytest.mark.parametrize("case", ROWS_CASES)
+def test_conv2d_writes_exactly_the_stats_rows_the_query_promises(dev, case):
+    """Every kernel family, launched through the raw C ABI with `stats` pointing at a NaN-filled slab: exactly the rows
+    hd_conv2d_stats_rows / hd_conv2d_route promise are written, the row after them (and the guard rows behind it) stay untouched."""
+    import ctypes as C
+    from hallucidet_amd import ops, _abi
+    lib = _abi.load()
+    fam, cfg, N, H, W, C1, C2, Cout, K, stride, pad, up1 = case
+    Hin, Win = (2 * H, 2 * W) if up1 else (H, W)
+    Ho, Wo = (Hin + 2 * pad - K) // stride + 1, (Win + 2 * pad - K) // stride + 1
+    x, w = rnd(N, H, W, C1, seed=61).to(dev), rnd(Cout, K * K * (C1 + C2), scale=0.05, seed=62).to(dev)
+    x2 = rnd(N, Hin, Win, C2, seed=63).to(dev) if C2 else None
+    y = torch.empty(N, Ho, Wo, Cout, dtype=torch.float16, device=dev)
+    try:
+        if cfg == 64:
+            lib.hd_conv_tune_override(-1, -1, 64, -1)
+        else:
+            lib.hd_conv_tune_w8(cfg, 1)
+        a, route = _conv_args(x, w, y, x2=x2, K=K, stride=stride, pad=pad, up1=up1)
+        rows = lib.hd_conv2d_stats_rows(C.byref(a))
+        assert route[0] == fam and rows == route[6] > 0, (route, rows)
+        if 18 <= cfg <= 20:
+            assert (route[1], route[2]) == {18: (4, 40), 19: (8, 40), 20: (4, 24)}[cfg]
+        elif 10 <= cfg <= 13:
+            assert route[1] == cfg - 10
+        slab = torch.full((rows + 4, 2, Cout), float("nan"), device=dev)
+        a.stats = ops.ptr(slab)
+        ops.check(lib.hd_conv2d(C.byref(a), ops._stream()), "hd_conv2d")
+        torch.cuda.synchronize()
+    finally:
+        lib.hd_conv_tune_w8(-1, 1)
+        lib.hd_conv_tune_override(-1, -1, -1, -1)
+    assert bool(torch.isfinite(slab[:rows]).all()), "a promised row was not written"
+    assert bool(torch.isnan(slab[rows]).all()) and bool(torch.isnan(slab[rows:]).all()), "a row past the promised ones was written"
+    assert bool(torch.isfinite(y).all())
+
+
+@pytest.mark.parametrize("hw", [(3, 8), (1, 16)])
+def test_batchnorm_backward_sums_on_the_upsample_concat_128_to_32_shapes(dev, hw):
+    """bs_* on a 3x3 / up1 / 64 + 64 -> 32 problem: the register-resident cat kernel does not implement the sums, so the launch runs on an
+    8-wave tile whose row count differs from the cat kernel's (3 x 8: 2 rows against 1; 1 x 16: 1 against 2).  ops.conv2d asks for the rows
+    with bs_* filled: the slab has the rows of the launch, their sums are hd_bn_bwd_reduce's on the stored dz, and dz is ATen's fp32
+    convolution of the gathered input."""
+    import ctypes as C
+    from hallucidet_amd import ops, _abi
+    lib = _abi.load()
+    Hs, Ws = hw
+    N, H, W, Cc = 1, 2 * hw[0], 2 * hw[1], 32
+    a_lo, skip, w = rnd(N, Hs, Ws, 64, seed=71).to(dev), rnd(N, H, W, 64, seed=72).to(dev), rnd(Cc, 9 * 128, scale=1.0 / 34.0, seed=73).to(dev)
+    g = torch.Generator().manual_seed(74)
+    y_u = torch.randn(N, H, W, Cc, generator=g).half().to(dev)
+    mean, invstd = torch.randn(Cc, generator=g).mul(0.1).to(dev), (torch.rand(Cc, generator=g) + 0.5).to(dev)
+    gamma, beta = (torch.rand(Cc, generator=g) + 0.5).to(dev), torch.randn(Cc, generator=g).mul(0.2).to(dev)
+    bs = dict(y=y_u, z=None, mean=mean, invstd=invstd, gamma=gamma, beta=beta, relu=True)
+    dz = ops.conv2d(a_lo, w, 3, 3, x2=skip, up1=True, pad=1, bstat=bs)
+    assert bs["part"] is not None, "hd_conv2d_bstat_ok says these problems run in a kernel that implements the sums"
+    blk, _ = _conv_args(a_lo, w, dz, x2=skip, up1=True)
+    blk.stats, blk.bs_y, blk.bs_mean, blk.bs_invstd = ops.ptr(bs["part"]), ops.ptr(y_u), ops.ptr(mean), ops.ptr(invstd)
+    route = (C.c_int32 * 8)()
+    ops.check(lib.hd_conv2d_route(C.byref(blk), route), "hd_conv2d_route")
+    assert route[0] in (6, 7) and bs["part"].shape[0] == route[6]
+    part = torch.empty(64, 2 * Cc, device=dev)
+    ops.check(lib.hd_bn_bwd_reduce(ops.ptr(dz), None, ops.ptr(y_u), ops.ptr(mean), ops.ptr(invstd), ops.ptr(gamma), ops.ptr(beta),
+                                   ops.ptr(part), 64, N * H * W, Cc, 1, ops._stream()), "hd_bn_bwd_reduce")
+    got, want = bs["part"].double().sum(0), part.double().sum(0)
+    print("bs sums: max difference %.3g, largest sum %.3g" % (float((got - want).abs().max()), float(want.abs().max())))
+    assert float((got - want).abs().max()) <= 2e-5 * float(want.abs().max()), (float((got - want).abs().max()), float(want.abs().max()))
+    up = a_lo.float().permute(0, 3, 1, 2).repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
+    cat = torch.cat([up, skip.float().permute(0, 3, 1, 2)], dim=1)
+    ref = torch.nn.functional.conv2d(cat, w.float().view(Cc, 3, 3, 128).permute(0, 3, 1, 2), padding=1).permute(0, 2, 3, 1)
+    err = (dz.float() - ref).abs()
+    print("dz: max error %.3g" % float(err.max()))
+    assert bool((err <= 2e-3 + 4e-3 * ref.abs()).all()), float(err.max())
