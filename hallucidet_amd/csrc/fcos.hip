@@ -12,8 +12,11 @@ constexpr int GB = 1024;   // GroupNorm block: (C/8) channel vectors x pixel lan
 // ---------------------------------------------------------------------------------------------------------------------
 // GroupNorm over NHWC f16 with EIGHT channels per group (GroupNorm(32, 256): a group is one 16-byte channel vector of a pixel).
 // One block per image: thread = (pixel lane, channel vector); consecutive threads read consecutive 16 B (a pixel's 512 B row).
-// Statistics in fp32 (biased variance, as torch.nn.functional.group_norm), saved as stat[n][g] = (mean, rstd).
-// The second pass re-reads x from L2 (a level of one image is at most 740 KB).
+// Statistics in fp32 (biased variance, as torch.nn.functional.group_norm), saved as stat[n][g] = (mean, rstd).  The variance is the
+// mean of (x - mean)^2, taken in a second reduction once the mean is known: the single-pass E[x^2] - mean^2 cancels in fp32 as soon
+// as |mean| >> std (rstd off by 1e-2 at |mean| / std = 256, by an order of magnitude on a constant group), the centred form stays
+// within a few fp32 ulps of the two-pass float64 value.  Both reductions add lane partials in a fixed order (deterministic).
+// The variance and the apply pass re-read x from L2 (a level of one image is at most 740 KB).
 __global__ __launch_bounds__(GB) void groupnorm8_fwd_kernel(const f16* __restrict__ x, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, f16* __restrict__ y, float* __restrict__ stat,
                                                             int HW, int C, float eps, int relu) {
@@ -23,36 +26,44 @@ __global__ __launch_bounds__(GB) void groupnorm8_fwd_kernel(const f16* __restric
   const int v = threadIdx.x % vecs, pl = threadIdx.x / vecs;
   const int n = blockIdx.x;
   const f16* xn = x + (size_t)n * HW * C;
-  float s = 0.f, q = 0.f;
+  float s = 0.f;
+  for (int p = pl; p < HW; p += PL) {
+    const f16x8 a = *reinterpret_cast<const f16x8*>(xn + (size_t)p * C + v * 8);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += (float)a[k];
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  if (pl == 0) {
+    float ts = 0.f;
+    for (int i = 0; i < PL; ++i) ts += red[i * vecs + v];               // fixed order: deterministic
+    st[v * 2] = ts / (float)(HW * 8);
+  }
+  __syncthreads();
+  const float m = st[v * 2];
+  float q = 0.f;
   for (int p = pl; p < HW; p += PL) {
     const f16x8 a = *reinterpret_cast<const f16x8*>(xn + (size_t)p * C + v * 8);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      const float f = (float)a[k];
-      s += f;
-      q += f * f;
+      const float d = (float)a[k] - m;
+      q += d * d;
     }
   }
-  red[threadIdx.x * 2] = s;
-  red[threadIdx.x * 2 + 1] = q;
+  red[GB + threadIdx.x] = q;                     // the second half of red[]: no lane still reads the first
   __syncthreads();
   if (pl == 0) {
-    float ts = 0.f, tq = 0.f;
-    for (int i = 0; i < PL; ++i) {               // fixed order: deterministic
-      ts += red[(i * vecs + v) * 2];
-      tq += red[(i * vecs + v) * 2 + 1];
-    }
-    const float m = ts / (float)(HW * 8);
-    float var = tq / (float)(HW * 8) - m * m;
+    float tq = 0.f;
+    for (int i = 0; i < PL; ++i) tq += red[GB + i * vecs + v];
+    float var = tq / (float)(HW * 8);
     if (var < 0.f) var = 0.f;
     const float r = rsqrtf(var + eps);
-    st[v * 2] = m;
     st[v * 2 + 1] = r;
     stat[((size_t)n * vecs + v) * 2] = m;
     stat[((size_t)n * vecs + v) * 2 + 1] = r;
   }
   __syncthreads();
-  const float m = st[v * 2], r = st[v * 2 + 1];
+  const float r = st[v * 2 + 1];
   float ga[8], be[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
