@@ -16,7 +16,7 @@ LIB = os.path.join(LIBDIR, "libhallucidet_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wno-unused-result"]
 # sources built a second time with -DHD_STORE_F32 (fp32 activation storage, entry points suffixed _f32: csrc/hd_common.h)
-TWICE = ("elementwise.hip", "roi_align.hip", "fcos.hip")
+TWICE = ("elementwise.hip", "roi_align.hip", "fcos.hip", "image_transform.hip")
 
 
 def _sources():

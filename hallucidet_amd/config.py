@@ -138,6 +138,12 @@ class Config:
         # device) or whose images differ in shape stays on the DataLoader.  Default: off
         p.add_argument("--cache-dataset", type=str, default="none", choices=["none", "hbm"])
         p.add_argument("--cache-budget-gb", type=float, default=None, metavar="G")
+        # the detector's input transform (models/custom_generalized_transform.py): how the image is resized to the detector's fixed size
+        # -- 'nearest' is the reference's F.interpolate default and what parity is judged against; 'bilinear' is torchvision's own;
+        # 'bilinear_aa' adds its antialias filter -- and whether it is normalised first ('imagenet': torchvision's mean / std, for
+        # detectors whose weights expect it).  Neither is stored in a checkpoint: evaluate a detector with the flags it was trained with
+        p.add_argument("--detector-resize", type=str, default="nearest", choices=["nearest", "bilinear", "bilinear_aa"])
+        p.add_argument("--detector-norm", type=str, default="none", choices=["none", "imagenet"])
         p.add_argument("--perceptual", type=str, default=None)
         p.add_argument("--weight-perceptual-rgb", type=float, default=0.0)
         p.add_argument("--weight-perceptual-ir", type=float, default=0.0)
@@ -155,6 +161,22 @@ class Config:
         p.add_argument("--encoder-depth", type=int, default=5)
         p.add_argument('--hallucidet-path', type=str)
         return p.parse_args(argv)
+
+    @staticmethod
+    def detector_norm_stats(name):
+        """--detector-norm -> (image_mean, image_std) for Detector / the Lit modules; 'none' -> (None, None): the reference's 0 / 1."""
+        if name in (None, "none"):
+            return None, None
+        if name == "imagenet":
+            from .resample import IMAGENET_MEAN, IMAGENET_STD
+            return list(IMAGENET_MEAN), list(IMAGENET_STD)
+        raise ValueError("unknown detector norm %r (none / imagenet)" % (name,))
+
+    @staticmethod
+    def transform_kwargs(args):
+        """The Lit modules' transform keywords from --detector-resize / --detector-norm."""
+        mean, std = Config.detector_norm_stats(args.detector_norm)
+        return dict(resize_mode=args.detector_resize, image_mean=mean, image_std=std)
 
     @staticmethod
     def cache_kwargs(args, device):

@@ -245,6 +245,9 @@ class DetectorStepGraph:
         pixel = lit.pixel_setup()                      # (kind, w_rgb, w_ir) of the pixel loss, None when off (the key is then unchanged)
         if pixel is not None:
             key = key + (pixel,)
+        how = getattr(lit.detector.transform, "_how", None)   # (mode, mean, std) of --detector-resize / --detector-norm, None for the reference's
+        if how is not None:
+            key = key + (("resize",) + how,)
         e = self.entries.get(key)
         # the loss scale of this step: GradScaler order (the overflow check of step t decides the scale of step t+1), resolved
         # BEFORE the replay because the scaled backward pass is inside the graph

@@ -5,6 +5,11 @@ Same class name, constructor keywords, `forward(images, targets) -> (ImageList, 
 batch_images) is ONE fused kernel: NCHW fp32 -> nearest resize -> NHWC fp16 (hd_nchw_to_nhwc_resize), differentiable
 through hd_nchw_to_nhwc_resize_bwd so the detector loss reaches the hallucination network.
 
+`interpolation="bilinear"` (torchvision's own mode, which the reference commented out) or `"bilinear_aa"` (the same with antialias=True),
+and `image_mean` / `image_std` other than 0 / 1, go through hd_image_resample / hd_image_resample_bwd instead (csrc/image_transform.hip:
+host tap tables, normalise then resample); the default launches exactly the kernels above.  Boxes are rescaled by the same ratios in
+every mode.
+
 `ImageList.tensors` holds the batched detector input in the layout the HIP backbone consumes
 (NHWC fp16, channels padded 3 -> 8); `ImageList.image_sizes` is the reference's list of (H, W).
 """
@@ -14,6 +19,7 @@ import torch
 from torch import nn, Tensor
 
 from .. import ops
+from ..resample import MODES, normalize_stats
 
 
 class ImageList:
@@ -27,15 +33,22 @@ class ImageList:
 
 
 class _ResizeFn(torch.autograd.Function):
+    """`how` = None: the reference's transform (nearest, mean 0 / std 1) through hd_nchw_to_nhwc_resize / _bwd; otherwise
+    (mode, mean, std) through hd_image_resample / _bwd."""
+
     @staticmethod
-    def forward(ctx, x, Ho, Wo):
-        ctx.shape = tuple(x.shape)
-        return ops.nchw_to_nhwc_resize(x, Ho, Wo, 8)
+    def forward(ctx, x, Ho, Wo, how=None):
+        ctx.shape, ctx.how = tuple(x.shape), how
+        if how is None:
+            return ops.nchw_to_nhwc_resize(x, Ho, Wo, 8)
+        return ops.image_resample(x, Ho, Wo, how[0], how[1], how[2])
 
     @staticmethod
     def backward(ctx, dy):
         N, C, H, W = ctx.shape
-        return ops.nchw_to_nhwc_resize_bwd(dy.contiguous(), N, C, H, W, 1.0), None, None
+        if ctx.how is None:
+            return ops.nchw_to_nhwc_resize_bwd(dy.contiguous(), N, C, H, W, 1.0), None, None, None
+        return ops.image_resample_bwd(dy.contiguous(), N, C, H, W, ctx.how[0], ctx.how[2], 1.0), None, None, None
 
 
 class _ResizeManyFn(torch.autograd.Function):
@@ -44,23 +57,30 @@ class _ResizeManyFn(torch.autograd.Function):
     gradient get one."""
 
     @staticmethod
-    def forward(ctx, Ho, Wo, *xs):
-        ctx.shapes = [tuple(x.shape) for x in xs]
+    def forward(ctx, Ho, Wo, how, *xs):
+        ctx.shapes, ctx.how = [tuple(x.shape) for x in xs], how
         n = sum(s[0] for s in ctx.shapes)
         y = torch.empty((n, Ho, Wo, 8), dtype=ops.act_dtype(), device=xs[0].device)
         lo = 0
         for x in xs:
-            ops.nchw_to_nhwc_resize(x, Ho, Wo, 8, out=y[lo:lo + x.shape[0]])
+            if how is None:
+                ops.nchw_to_nhwc_resize(x, Ho, Wo, 8, out=y[lo:lo + x.shape[0]])
+            else:
+                ops.image_resample(x, Ho, Wo, how[0], how[1], how[2], out=y[lo:lo + x.shape[0]])
             lo += x.shape[0]
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        grads, lo = [], 0
+        grads, lo, how = [], 0, ctx.how
         for i, (N, C, H, W) in enumerate(ctx.shapes):
-            grads.append(ops.nchw_to_nhwc_resize_bwd(dy[lo:lo + N].contiguous(), N, C, H, W, 1.0) if ctx.needs_input_grad[2 + i] else None)
+            g = None
+            if ctx.needs_input_grad[3 + i]:
+                d = dy[lo:lo + N].contiguous()
+                g = ops.nchw_to_nhwc_resize_bwd(d, N, C, H, W, 1.0) if how is None else ops.image_resample_bwd(d, N, C, H, W, how[0], how[2], 1.0)
+            grads.append(g)
             lo += N
-        return (None, None) + tuple(grads)
+        return (None, None, None) + tuple(grads)
 
 
 _RATIO_CACHE = {}
@@ -106,9 +126,24 @@ def resize_boxes_many(box_list, original_size, new_size):
     return list(out.split(n, 0))
 
 
+def configure_transform(detector, resize_mode="nearest", image_mean=None, image_std=None):
+    """Give `detector.transform` (a fixed-size CustomGeneralizedRCNNTransform) another resize mode / normalisation, keeping its size:
+    what EncoderDecoderLit / DetectorLit do with a detector they were handed.  None statistics mean the reference's 0 / 1."""
+    t = detector.transform
+    if not isinstance(t, CustomGeneralizedRCNNTransform):
+        raise TypeError("hallucidet_amd: resize_mode / image_mean / image_std need the fixed-size transform (got %s)" % type(t).__name__)
+    new = CustomGeneralizedRCNNTransform(min_size=t.min_size, max_size=t.max_size, image_mean=[0.0] if image_mean is None else image_mean,
+                                         image_std=[1.0] if image_std is None else image_std, size_divisible=t.size_divisible,
+                                         fixed_size=t.fixed_size, interpolation=resize_mode, _skip_resize=t._skip_resize)
+    new.train(t.training)
+    detector.transform = new
+    return new
+
+
 class CustomGeneralizedRCNNTransform(nn.Module):
     def __init__(self, min_size: int, max_size: int, image_mean: List[float], image_std: List[float],
-                 size_divisible: int = 32, fixed_size: Optional[Tuple[int, int]] = None, **kwargs: Any):
+                 size_divisible: int = 32, fixed_size: Optional[Tuple[int, int]] = None, interpolation: str = "nearest",
+                 **kwargs: Any):
         super().__init__()
         if not isinstance(min_size, (list, tuple)):
             min_size = (min_size,)
@@ -118,9 +153,14 @@ class CustomGeneralizedRCNNTransform(nn.Module):
         self._skip_resize = kwargs.pop("_skip_resize", False)
         if fixed_size is None:
             raise NotImplementedError("hallucidet_amd: the hot path always passes fixed_size (detector.py:43-48)")
-        if any(float(m) != 0.0 for m in image_mean) or any(float(s) != 1.0 for s in image_std):
-            raise NotImplementedError("hallucidet_amd: fused transform implements mean 0 / std 1 (detector.py:45-46), "
-                                      "for which normalize is the identity")
+        if interpolation not in MODES:
+            raise ValueError("hallucidet_amd: interpolation must be one of %s (got %r)" % (", ".join(MODES), interpolation))
+        self.interpolation = interpolation
+        self.mean, self.std = normalize_stats(image_mean, image_std, 3)      # length 1 (broadcast) or 3
+        # the reference's transform -- nearest, mean 0 / std 1, for which normalize is the identity (detector.py:45-46) -- keeps the
+        # kernels it always had; every other setting goes through hd_image_resample / hd_image_resample_bwd
+        self._legacy = interpolation == "nearest" and all(m == 0.0 for m in self.mean) and all(s == 1.0 for s in self.std)
+        self._how = None if self._legacy else (interpolation, self.mean, self.std)
 
     def forward(self, images, targets: Optional[List[Dict[str, Tensor]]] = None):
         imgs = [img for img in images]
@@ -140,7 +180,7 @@ class CustomGeneralizedRCNNTransform(nn.Module):
         x = x.float().contiguous()
         h, w = x.shape[-2:]
         Wo, Ho = self.fixed_size[0], self.fixed_size[1]           # size = [fixed_size[1], fixed_size[0]] (:65-66)
-        y = _ResizeFn.apply(x, Ho, Wo)
+        y = _ResizeFn.apply(x, Ho, Wo, self._how)
         if targets is not None:
             for t, b in zip(targets, resize_boxes_many([t["boxes"] for t in targets], (h, w), (Ho, Wo))):
                 t["boxes"] = b
@@ -160,7 +200,7 @@ class CustomGeneralizedRCNNTransform(nn.Module):
             xs.append(ops.as_dense_planes_f32(b))
         h, w = xs[0].shape[-2:]
         Wo, Ho = self.fixed_size[0], self.fixed_size[1]
-        y = _ResizeManyFn.apply(Ho, Wo, *xs)
+        y = _ResizeManyFn.apply(Ho, Wo, self._how, *xs)
         if targets is not None:
             targets = [{k: v for k, v in t.items()} for t in targets]
             for t, b in zip(targets, resize_boxes_many([t["boxes"] for t in targets], (h, w), (Ho, Wo))):
@@ -180,4 +220,4 @@ class CustomGeneralizedRCNNTransform(nn.Module):
 
     def __repr__(self) -> str:
         return (f"{self.__class__.__name__}(\n    Normalize(mean={self.image_mean}, std={self.image_std})"
-                f"\n    Resize(fixed_size={self.fixed_size}, mode='nearest')\n)")
+                f"\n    Resize(fixed_size={self.fixed_size}, mode='{self.interpolation}')\n)")

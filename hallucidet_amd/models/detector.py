@@ -26,12 +26,20 @@ def _xavier_init(conv: torch.nn.Module):
 
 class Detector():
     def __init__(self, name='fasterrcnn_resnet50_fpn', pretrained=True, n_classes=2, size=300, batch_norm_eps=0.001,
-                 batch_norm_momentum=0.03, eval_path=None, modality=None, directly_coco=False):
+                 batch_norm_momentum=0.03, eval_path=None, modality=None, directly_coco=False, resize_mode="nearest",
+                 image_mean=None, image_std=None):
+        """resize_mode ('nearest' | 'bilinear' | 'bilinear_aa') and image_mean / image_std (None = the reference's [0.0] / [1.0]; 1 or 3
+        entries) configure the fixed-size transform (--detector-resize / --detector-norm); nothing of them is stored in a checkpoint."""
         self.detector = Detector.select_detector(detector_name=name, pretrained=pretrained)
+        if directly_coco and (resize_mode != "nearest" or image_mean is not None or image_std is not None):
+            raise ValueError("hallucidet_amd: resize_mode / image_mean / image_std configure the fixed-size transform, which "
+                             "directly_coco does not install")
         if not directly_coco:
-            self.detector.transform = self.change_generalized_transform(min_size=size, max_size=size, image_mean=[0.0],
-                                                                        image_std=[1.0], size_divisible=1,
-                                                                        fixed_size=(size, size))
+            self.detector.transform = self.change_generalized_transform(min_size=size, max_size=size,
+                                                                        image_mean=[0.0] if image_mean is None else image_mean,
+                                                                        image_std=[1.0] if image_std is None else image_std,
+                                                                        size_divisible=1, fixed_size=(size, size),
+                                                                        interpolation=resize_mode)
             if 'fasterrcnn' in name:
                 in_features = self.detector.roi_heads.box_predictor.cls_score.in_features
                 self.detector.roi_heads.box_predictor = detection.FastRCNNPredictor(in_features, n_classes)
@@ -56,9 +64,9 @@ class Detector():
                     print("Select model is not compatible with the detector (Requires: .bin dict)")
 
     def change_generalized_transform(self, min_size=300, max_size=300, image_mean=[0.0], image_std=[1.0], size_divisible=1,
-                                     fixed_size=(300, 300)):
+                                     fixed_size=(300, 300), interpolation="nearest"):
         return CustomGeneralizedRCNNTransform(min_size=min_size, max_size=max_size, image_mean=image_mean, image_std=image_std,
-                                              size_divisible=size_divisible, fixed_size=fixed_size)
+                                              size_divisible=size_divisible, fixed_size=fixed_size, interpolation=interpolation)
 
     @staticmethod
     def calculate_loss(detector, outs, targets, train_det=False, model_name='fasterrcnn'):

@@ -10,10 +10,13 @@ import ctypes as C
 import os
 import threading
 
+import numpy as np
 import torch
 
 from . import _abi
+from . import resample as _resample
 from ._abi import ConvArgs, WgradArgs, check, ptr
+from .resample import resample_taps
 
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 
@@ -679,6 +682,98 @@ def nchw_to_nhwc_resize_bwd(dy, N, Cr, H, W, gscale=1.0):
     dx = torch.empty((N, Cr, H, W), dtype=torch.float32, device=dy.device)
     check(_abi.fn("hd_nchw_to_nhwc_resize_bwd", dy)(ptr(dy), ptr(dx), N, Cr, H, W, Ho, Wo, Cp, gscale, _stream()),
           "hd_nchw_to_nhwc_resize_bwd")
+    return dx
+
+
+_RESAMPLE_TABLES = {}
+
+
+def resample_tables(in_size, out_size, mode, device):
+    """Device copies of one axis' tap tables (hallucidet_amd.resample.resample_taps), checked at the C boundary and uploaded ONCE per
+    (in, out, mode, device).  The first use of a key must happen outside a stream capture (an upload cannot be captured): the detector
+    graph warms up eagerly before it captures, which is what provides it; a new key during a capture raises."""
+    device = torch.device(device)
+    key = (int(in_size), int(out_size), mode, device.type, device.index if device.index is not None else torch.cuda.current_device())
+    d = _RESAMPLE_TABLES.get(key)
+    if d is None:
+        t = resample_taps(in_size, out_size, mode)
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("hallucidet_amd.ops: the %s tap tables for %d -> %d are first needed inside a stream capture; run the "
+                               "transform once eagerly (a warm-up step) before capturing it" % (mode, in_size, out_size))
+        _resample.check_taps(t)
+        up = lambda a: torch.from_numpy(np.array(a)).to(device)           # (a writable copy: the cached host tables are read-only)
+        d = {"T": t.T, "nnz": t.nnz, "start": up(t.start), "count": up(t.count), "weight": up(t.weight), "weight_lo": up(t.weight_lo),
+             "rstart": up(t.rstart), "rout": up(t.rout), "rweight": up(t.rweight)}
+        _RESAMPLE_TABLES[key] = d
+    return d
+
+
+def _stats_arrays(mean, std, Cr):
+    """Host float arrays of Cr entries for the C boundary (None -> NULL = 0 / 1)."""
+    def arr(v, name):
+        if v is None:
+            return None
+        v = [float(a) for a in v]
+        if len(v) == 1:
+            v = v * Cr
+        if len(v) != Cr:
+            raise ValueError("image_resample: %s must have 1 or %d entries (got %d)" % (name, Cr, len(v)))
+        return (C.c_float * Cr)(*v)
+    m, s = arr(mean, "mean"), arr(std, "std")
+    if s is not None and any(not (a > 0.0) for a in s):
+        raise ValueError("image_resample: std must be > 0 in every channel (got %s)" % (list(s),))
+    return m, s
+
+
+def image_resample(x, Ho, Wo, mode, mean=None, std=None, Cp=8, out=None, dtype=None):
+    """hd_image_resample: NCHW fp32 [N, Cr, H, W] (contiguous, or dense planes with any image / channel stride such as the stride-0
+    channel view of a one-plane IR batch) -> NHWC [N, Ho, Wo, 8] in the storage type, resized with `mode` ('nearest' | 'bilinear' |
+    'bilinear_aa') after (x - mean[c]) / std[c]; pad channels zero.  `out`: write into this tensor (e.g. a slice along dim 0 of a larger
+    batch); `dtype`: storage type of a new one."""
+    _need_cuda(x, out)
+    if x.dim() != 4:
+        raise ValueError("image_resample: x must be [N, C, H, W] (got %s)" % (tuple(x.shape),))
+    N, Cr, H, W = x.shape
+    if x.dtype != torch.float32:
+        raise TypeError("image_resample: x must be float32 (got %s)" % x.dtype)
+    if Cp != 8 or not 1 <= Cr <= 8:
+        raise ValueError("image_resample: 1 .. 8 channels, padded to 8 (got Cr=%d Cp=%d)" % (Cr, Cp))
+    if not (x.is_contiguous() or (dense_planes(x) and x.stride(0) >= H * W and (x.stride(1) == 0 or x.stride(1) >= H * W))):
+        raise ValueError("image_resample: the H x W planes of x must be dense (strides %s); see ops.as_dense_planes_f32" % (tuple(x.stride()),))
+    if mode not in _resample.MODES:
+        raise ValueError("image_resample: mode must be one of %s (got %r)" % (", ".join(_resample.MODES), mode))
+    m, s = _stats_arrays(mean, std, Cr)
+    if out is None:
+        y = torch.empty((N, Ho, Wo, Cp), dtype=dtype or act_dtype(), device=x.device)
+    else:
+        y = out
+        if tuple(y.shape) != (N, Ho, Wo, Cp) or y.dtype not in (torch.float16, torch.float32) or not y.is_contiguous():
+            raise ValueError("image_resample: out must be a contiguous float16 / float32 tensor of shape %s" % ((N, Ho, Wo, Cp),))
+    ty, tx = resample_tables(H, Ho, mode, x.device), resample_tables(W, Wo, mode, x.device)
+    ns, cs = (Cr * H * W, H * W) if x.is_contiguous() else (x.stride(0), x.stride(1))
+    check(_abi.fn("hd_image_resample", y)(ptr(x), ns, cs, ptr(y), N, Cr, H, W, Ho, Wo, Cp, ptr(ty["start"]), ptr(ty["count"]), ptr(ty["weight"]),
+                                          ty["T"], ptr(tx["start"]), ptr(tx["count"]), ptr(tx["weight"]), tx["T"], m, s, ptr(ty["weight_lo"]), ptr(tx["weight_lo"]), _stream()),
+          "hd_image_resample")
+    return y
+
+
+def image_resample_bwd(dy, N, Cr, H, W, mode, std=None, gscale=1.0):
+    """hd_image_resample_bwd: dy NHWC [N, Ho, Wo, 8] (contiguous, storage type) -> dx NCHW fp32 [N, Cr, H, W], the gradient of
+    image_resample with respect to x times gscale."""
+    _need_cuda(dy)
+    if dy.dim() != 4 or dy.shape[0] != N or dy.shape[3] != 8 or not dy.is_contiguous():
+        raise ValueError("image_resample_bwd: dy must be a contiguous [%d, Ho, Wo, 8] tensor (got %s, strides %s)" % (N, tuple(dy.shape), tuple(dy.stride())))
+    if not 1 <= Cr <= 8:
+        raise ValueError("image_resample_bwd: 1 .. 8 channels (got %d)" % Cr)
+    if mode not in _resample.MODES:
+        raise ValueError("image_resample_bwd: mode must be one of %s (got %r)" % (", ".join(_resample.MODES), mode))
+    _, s = _stats_arrays(None, std, Cr)
+    _, Ho, Wo, Cp = dy.shape
+    ty, tx = resample_tables(H, Ho, mode, dy.device), resample_tables(W, Wo, mode, dy.device)
+    dx = torch.empty((N, Cr, H, W), dtype=torch.float32, device=dy.device)
+    check(_abi.fn("hd_image_resample_bwd", dy)(ptr(dy), ptr(dx), N, Cr, H, W, Ho, Wo, Cp, ptr(ty["rstart"]), ptr(ty["rout"]), ptr(ty["rweight"]),
+                                               ty["nnz"], ptr(tx["rstart"]), ptr(tx["rout"]), ptr(tx["rweight"]), tx["nnz"], s, float(gscale),
+                                               _stream()), "hd_image_resample_bwd")
     return dx
 
 

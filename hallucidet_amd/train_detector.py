@@ -18,6 +18,7 @@ from . import ops
 from .config import Config
 from .distributed import GradientAverager, broadcast_parameters
 from .models.cnnBasedThermalInfraredDA import IR_PREPROCESS_NAMES, CnnBasedThermalInfraredDA
+from .models.custom_generalized_transform import configure_transform
 from .models.detector import Detector
 from .optim import FusedAdam, LossScaler, ParamArena
 from .utils.utils import Utils
@@ -26,7 +27,7 @@ from .utils.utils import Utils
 class DetectorLit:
     def __init__(self, batch_size=4, wandb_logger=None, lr=0.0001, detector_name='fasterrcnn', pretrained=True, optimizer_name='adam',
                  modality=None, directly_coco=False, detector=None, device='cuda', loss_scale=1024.0, precision=16, map_device='cpu',
-                 ir_preprocess='none', media=None):
+                 ir_preprocess='none', media=None, resize_mode='nearest', image_mean=None, image_std=None):
         if not any(k in detector_name for k in ('fasterrcnn', 'retinanet', 'fcos')):
             raise ValueError("unknown detector %r (fasterrcnn / retinanet / fcos)" % (detector_name,))
         self.wandb_logger, self.lr, self.batch_size = wandb_logger, lr, batch_size
@@ -42,7 +43,11 @@ class DetectorLit:
         self.current_epoch = 0                # set by Trainer before validate / test: names the media files
         self.detector = detector if detector is not None else Detector(name=detector_name, pretrained=pretrained,
                                                                        n_classes=getattr(getattr(Config, 'Dataset', None), 'n_classes', 2), size=Config.Detector.input_size,
-                                                                       modality=modality, directly_coco=directly_coco).detector
+                                                                       modality=modality, directly_coco=directly_coco, resize_mode=resize_mode,
+                                                                       image_mean=image_mean, image_std=image_std).detector
+        self.resize_mode = resize_mode        # --detector-resize / --detector-norm: the transform's mode and statistics; not stored in checkpoints
+        if detector is not None and (resize_mode != 'nearest' or image_mean is not None or image_std is not None):
+            configure_transform(self.detector, resize_mode, image_mean, image_std)
         self.detector.fused_passes = False
         # precision 32 (the reference's default, src/config/config.py:149 -> train_detector.py:387): fp32 storage, no loss scaling
         if int(precision) not in (16, 32):

@@ -15,6 +15,7 @@ from .config import Config
 from .distributed import GradientAverager, broadcast_parameters, exchange_and_step
 from .losses.losses import PixelTerms, Reconstruction
 from .models.cnnBasedThermalInfraredDA import IR_PREPROCESS_NAMES, CnnBasedThermalInfraredDA
+from .models.custom_generalized_transform import configure_transform
 from .models.detector import Detector
 from .models.encoder_decoder import EncoderDecoder
 from .optim import LossScaler
@@ -52,7 +53,7 @@ class EncoderDecoderLit(nn.Module):
     def __init__(self, batch_size=4, wandb_logger=None, model_name='resnet34', in_channels=3, output_channels=3, lr=0.0001,
                  loss_pixel=None, loss_perceptual=None, detector_name='fasterrcnn', train_det=False, fuse_data='none',
                  scheduler_on=False, detector=None, precision=16, device='cuda', use_graphs=True, map_device='cpu',
-                 ir_preprocess='none', media=None):
+                 ir_preprocess='none', media=None, resize_mode='nearest', image_mean=None, image_std=None):
         super().__init__()
         self.model_name, self.wandb_logger = model_name, wandb_logger
         self.in_channels, self.output_channels = in_channels, output_channels
@@ -82,7 +83,13 @@ class EncoderDecoderLit(nn.Module):
                                               output_channels=self.output_channels,
                                               segmentation_head=Config.EncoderDecoder.decoder_head).encoder_decoder
         self.detector = detector if detector is not None else Detector(name=detector_name, pretrained=False, n_classes=2,
-                                                                       size=Config.Detector.input_size).detector
+                                                                       size=Config.Detector.input_size, resize_mode=resize_mode,
+                                                                       image_mean=image_mean, image_std=image_std).detector
+        # how the detector's transform resizes (and normalises) its input: 'nearest' with no statistics is the reference's and leaves a
+        # detector that was handed in as it is; anything else re-configures its transform (--detector-resize / --detector-norm)
+        self.resize_mode = resize_mode
+        if detector is not None and (resize_mode != 'nearest' or image_mean is not None or image_std is not None):
+            configure_transform(self.detector, resize_mode, image_mean, image_std)
         self.detector.eval()
         for p in self.detector.parameters():
             p.requires_grad = False

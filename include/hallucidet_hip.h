@@ -324,6 +324,29 @@ int hd_nchw_to_nhwc_resize_strided(const float* x, int64_t nstride, int64_t cstr
 /* backward of the above: dx NCHW f32 (zero where no destination pixel selects the source) */
 int hd_nchw_to_nhwc_resize_bwd(const void* dy, float* dx, int N, int Cr, int H, int W, int Ho, int Wo, int Cp,
                                float gscale, void* stream);
+/* Detector-input resize with separable tap tables and per-channel normalisation (csrc/image_transform.hip; --detector-resize):
+ * NCHW f32 x (image / channel strides in elements, rows dense; cstride == 0 broadcasts plane 0) -> NHWC f16 y [N,Ho,Wo,8],
+ *   y[n,ho,wo,c] = sum_i sum_j yweight[ho][i] * xweight[wo][j] * (x[n,c,ystart[ho]+i,xstart[wo]+j] - mean[c]) * (1/std[c]),
+ * channels >= Cr zero; fp32 instructions, rows ascending then columns ascending, the sum carried as a high + low pair of floats and its
+ * high part stored (the exact sum rounded once to fp32, then to the storage type).  Tables of an axis (DEVICE pointers): start[out],
+ * count[out] (int32), weight[out][T] (fp32, zero past the count), T <= 32; weight_lo[out][T] = fp32(W - weight), the part of the float64
+ * weight W that fp32 drops (both NULL: zero).  mean / std: HOST pointers to Cr floats, NULL = 0 / 1.
+ * y may be a slice of a larger batch.  Indices are clamped in the kernel: no table content can make it read outside x. */
+int hd_image_resample(const float* x, int64_t nstride, int64_t cstride, void* y, int N, int Cr, int H, int W, int Ho, int Wo, int Cp,
+                      const int* ystart, const int* ycount, const float* yweight, int Ty, const int* xstart, const int* xcount,
+                      const float* xweight, int Tx, const float* mean, const float* std_, const float* yweight_lo, const float* xweight_lo,
+                      void* stream);
+/* its gradient, gather form (one writer per element, no atomics): dx NCHW f32 [N,Cr,H,W] (contiguous) =
+ * (gscale / std[c]) * sum over the transposed tables, output rows ascending then output columns ascending, of wy * wx * dy[n,ho,wo,c].
+ * Transposed tables of an axis (DEVICE pointers, CSR over the input index): rstart[in+1], rout[nnz] (ascending within a row),
+ * rweight[nnz] -- the forward form's entries.  dy NHWC [N,Ho,Wo,8] contiguous; Cr <= 8; std: HOST pointer or NULL. */
+int hd_image_resample_bwd(const void* dy, float* dx, int N, int Cr, int H, int W, int Ho, int Wo, int Cp, const int* yrstart,
+                          const int* yrout, const float* yrweight, int ynnz, const int* xrstart, const int* xrout, const float* xrweight,
+                          int xnnz, const float* std_, float gscale, void* stream);
+/* host-side check of one axis' tables (HOST pointers; no GPU work): taps inside the input, transposed indices inside the output and
+ * sorted, transposed entries == forward entries, |weight_lo| (may be NULL) <= 2^-24 |weight|.  Call it before uploading a table. */
+int hd_resample_taps_check(const int* start, const int* count, const float* weight, int in_size, int out_size, int T, const int* rstart,
+                           const int* rout, const float* rweight, int nnz, const float* weight_lo);
 /* NHWC f16 [N,H,W,Cp] -> NCHW f32 [N,Cr,H,W] */
 int hd_nhwc_to_nchw(const void* x, float* y, int N, int Cr, int H, int W, int Cp, void* stream);
 /* y = a + nearest_resize(b -> a's size)  (FPN top-down path, torchvision FeaturePyramidNetwork [EXT]) */
@@ -729,6 +752,13 @@ int hd_nchw_to_nhwc_resize_f32(const float* x, void* y, int N, int Cr, int H, in
 int hd_nchw_to_nhwc_resize_strided_f32(const float* x, int64_t nstride, int64_t cstride, void* y, int N, int Cr, int H, int W, int Ho,
                                        int Wo, int Cp, void* stream);
 int hd_nchw_to_nhwc_resize_bwd_f32(const void* dy, float* dx, int N, int Cr, int H, int W, int Ho, int Wo, int Cp, float gscale, void* stream);
+int hd_image_resample_f32(const float* x, int64_t nstride, int64_t cstride, void* y, int N, int Cr, int H, int W, int Ho, int Wo, int Cp,
+                          const int* ystart, const int* ycount, const float* yweight, int Ty, const int* xstart, const int* xcount,
+                          const float* xweight, int Tx, const float* mean, const float* std_, const float* yweight_lo,
+                          const float* xweight_lo, void* stream);
+int hd_image_resample_bwd_f32(const void* dy, float* dx, int N, int Cr, int H, int W, int Ho, int Wo, int Cp, const int* yrstart,
+                              const int* yrout, const float* yrweight, int ynnz, const int* xrstart, const int* xrout,
+                              const float* xrweight, int xnnz, const float* std_, float gscale, void* stream);
 int hd_nhwc_to_nchw_f32(const void* x, float* y, int N, int Cr, int H, int W, int Cp, void* stream);
 int hd_upsample_add_f32(const void* a, const void* b, void* y, int N, int H, int W, int C, int Hb, int Wb, void* stream);
 int hd_upsample_add_bwd_f32(const void* dy, void* db, int N, int H, int W, int C, int Hb, int Wb, int accumulate, void* stream);
