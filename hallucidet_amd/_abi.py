@@ -85,6 +85,7 @@ PROTOTYPES = {
     "hd_conv_nominal_batch": (C.c_int, [C.c_int]),
     "hd_gemm_w8_mode": (C.c_int, [C.c_int]),
     "hd_wgrad_w8_blocks": (C.c_int, [C.POINTER(WgradArgs)]),
+    "hd_wgrad_route": (C.c_int, [C.POINTER(WgradArgs), C.POINTER(c_i32)]),
     "hd_wgrad": (C.c_int, [C.POINTER(WgradArgs), vp]),
     "hd_wgrad_multi": (C.c_int, [C.POINTER(WgradArgs), C.c_int, vp]),
     "hd_wgrad_direct_ok": (C.c_int, [C.POINTER(WgradArgs)]),

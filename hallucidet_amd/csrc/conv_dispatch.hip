@@ -516,7 +516,8 @@ extern "C" int hd_conv2d_wgrad(const hd_conv_args* a, const hd_wgrad_args* wa, v
   if (rc) return rc;
   const Route r = route(p);
   HD_CHECK_ARG(!p.pool2 || implements_pool2(p, r), "hd_conv2d_wgrad: out_pool2 is not implemented for this problem; ask hd_conv2d_pool2_ok first");
-  if (fuse_on && carries_wgrad(p, r) && hd_wgrad_takes_w8(wa)) {
+  int32_t wr[8];      // hd_wgrad_route: wr[5] = the weight gradient runs in the 8-wave kernel (a refused block falls through to hd_wgrad's refusal)
+  if (fuse_on && carries_wgrad(p, r) && hd_wgrad_route(wa, wr) == HD_OK && wr[5]) {
     launch(p, r, (hipStream_t)stream, wa);
     HD_CHECK_LAUNCH();
     return HD_OK;

@@ -169,8 +169,6 @@ void hd_conv_launch_m160(ConvP& p, int th, int tw, hipStream_t s);      // (th, 
 void hd_conv_launch_m96_multi(ConvMulti& mp, hipStream_t s);              // several 4 x 24-pixel-tile problems in one grid
 // the same tile grid with the blocks of an 8-wave weight gradient behind it (one launch; conv3x3_w8.hip)
 void hd_conv_launch_p8_wgrad(ConvP& p, int cfg, const hd_wgrad_args* wa, hipStream_t s);
-// wgrad.hip: would hd_wgrad run this weight gradient in the 8-wave patch-staged kernel?
-bool hd_wgrad_takes_w8(const hd_wgrad_args* a);
 // conv3x3_small.hip: 3x3 / stride 1 / pad 1, Cin in {8,16,32}, Cout in {16,32}, plain NHWC f16 output (+ BN partial sums)
 bool hd_conv_small_eligible(const ConvP& p);
 bool hd_conv_small_pool2_ok(const ConvP& p);

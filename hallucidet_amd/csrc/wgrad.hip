@@ -574,112 +574,122 @@ extern "C" int hd_wgrad_tune_override(int tm) {
   return HD_OK;
 }
 
-// wgrad3x3_small.hip: 3x3 / s1 / p1, Cin in {16,32}, Cout <= 32 (HD_WGRAD_SMALL=0 or a tile override keeps the general kernel)
+// wgrad3x3_small.hip: 3x3 / s1 / p1, Cin in {16,32} or the 64 + 64 upsampled concat, Cout <= 32; 8 x 32-pixel tiles, one block per split
 bool hd_wgrad_small_eligible(const hd_wgrad_args* a);
 void hd_wgrad_small_launch(const hd_wgrad_args* a, hipStream_t s);
-// wgrad3x3_w8.hip: 3x3 / s1 / p1, >= 64 channels in and out: 8-wave patch-staged kernel (HD_WGRAD_W8=0 keeps the general kernel)
+// wgrad3x3_w8.hip: 3x3 / s1 / p1, multiples of 64 channels in and out: 8-wave patch-staged kernel, 16 x 8-pixel tiles, one block per
+// 64 x 64 weight tile and split; hd_wgrad_w8_launch_multi: several such problems as ONE grid
 bool hd_wgrad_w8_eligible(const hd_wgrad_args* a);
 void hd_wgrad_w8_launch(const hd_wgrad_args* a, hipStream_t s);
-extern "C" int hd_wgrad_w8_blocks(const hd_wgrad_args* a) {
-  if (!a) return 0;
-  static const char* env = getenv("HD_WGRAD_W8");
-  if ((env && env[0] == '0') || !hd_wgrad_w8_eligible(a)) return 0;
-  return ((a->C1 + a->C2) / 64) * (a->Cout / 64);
+void hd_wgrad_w8_launch_multi(const hd_wgrad_args* a, int n, hipStream_t s);
+
+// A/B knobs, read once: HD_WGRAD_W8=0 / HD_WGRAD_SMALL=0 keep the general kernel, HD_WGRAD_MULTI=0 launches hd_wgrad_multi's entries one by one
+struct WgKnobs { bool w8, small, multi; };
+static const WgKnobs& wg_knobs() {
+  auto on = [](const char* e) { return !(e && e[0] == '0'); };
+  static const WgKnobs k = {on(getenv("HD_WGRAD_W8")), on(getenv("HD_WGRAD_SMALL")), on(getenv("HD_WGRAD_MULTI"))};
+  return k;
 }
 
-extern "C" int hd_wgrad_direct_ok(const hd_wgrad_args* a) {
-  if (!a || a->nsplit != 1 || a->in_scale) return 0;
-  static const char* env8 = getenv("HD_WGRAD_W8");
-  static const bool w8_on = !(env8 && env8[0] == '0');
-  return (w8_on && g_wg_tm < 0 && !hd_wgrad_small_eligible(a) && hd_wgrad_w8_eligible(a)) ? 1 : 0;
+// THE routing decision: every entry point and query below asks here which kernel a problem runs in.
+enum WgFamily { WG_GENERAL, WG_SMALL, WG_SMALL_CAT, WG_W8 };
+struct WgRoute { int fam, tm, wtiles, ptiles; };      // tm: the general kernel's Cout tile; blocks per pixel split; pixel tiles the family walks
+static WgRoute wg_route(const hd_wgrad_args* a) {
+  const int Cin = a->C1 + a->C2;
+  // The two special domains are disjoint (small: Cout <= 32, 8-wave: Cout % 64 == 0), so neither test needs "and not the other".
+  // A tile override keeps both off; a raw operand (in_scale) is only implemented by the small kernel, whatever HD_WGRAD_SMALL says.
+  if (g_wg_tm < 0 && (wg_knobs().small || a->in_scale) && hd_wgrad_small_eligible(a))
+    return {a->x2 ? WG_SMALL_CAT : WG_SMALL, 0, 1, a->N * hd_cdiv(a->Ho, 8) * hd_cdiv(a->Wo, 32)};
+  if (g_wg_tm < 0 && wg_knobs().w8 && !a->in_scale && hd_wgrad_w8_eligible(a))
+    return {WG_W8, 0, (Cin / 64) * (a->Cout / 64), a->N * hd_cdiv(a->Ho, 16) * hd_cdiv(a->Wo, 8)};
+  const int tm = g_wg_tm > 0 ? g_wg_tm : (a->Cout > 64 ? 128 : (a->Cout > 32 ? 64 : 32));
+  return {WG_GENERAL, tm, hd_cdiv((int64_t)a->KH * a->KW * Cin, TN) * hd_cdiv(a->Cout, tm), hd_cdiv((int64_t)a->N * a->Ho * a->Wo, BP)};
 }
 
-bool hd_wgrad_takes_w8(const hd_wgrad_args* a) {
-  static const char* env8 = getenv("HD_WGRAD_W8");
-  static const bool w8_on = !(env8 && env8[0] == '0');
-  if (!a || !a->x || !a->dy || !(a->slab || (a->dw_oihw && a->nsplit == 1)) || a->nsplit < 1 || a->in_scale) return false;
-  if (g_wg_tm >= 0 || hd_wgrad_small_eligible(a)) return false;
-  return w8_on && hd_wgrad_w8_eligible(a);
-}
-
-extern "C" int hd_wgrad(const hd_wgrad_args* a, void* stream) {
-  HD_CHECK_ARG(a && a->x && a->dy && (a->slab || a->dw_oihw), "hd_wgrad: null pointer");
-  HD_CHECK_ARG(!a->dw_oihw || hd_wgrad_direct_ok(a), "hd_wgrad: dw_oihw (direct output) needs nsplit == 1 and the 8-wave 3x3 kernel (hd_wgrad_direct_ok)");
+// everything hd_wgrad refuses
+static int wg_accepts(const hd_wgrad_args* a, const WgRoute& r) {
+  HD_CHECK_ARG(a->x && a->dy && (a->slab || a->dw_oihw), "hd_wgrad: null pointer");
   HD_CHECK_ARG(a->C1 > 0 && a->C1 % 8 == 0 && a->C2 % 8 == 0 && a->Cout % 8 == 0, "hd_wgrad: channels must be multiples of 8");
   HD_CHECK_ARG((a->C2 == 0) == (a->x2 == nullptr), "hd_wgrad: x2/C2 mismatch");
   HD_CHECK_ARG(a->nsplit >= 1, "hd_wgrad: nsplit");
   HD_CHECK_ARG((a->in_scale == nullptr) == (a->in_shift == nullptr), "hd_wgrad: in_scale / in_shift must be given together");
-  {
-    static const char* env = getenv("HD_WGRAD_SMALL");
-    static const bool small_on = !(env && env[0] == '0');
-    if ((small_on || a->in_scale) && g_wg_tm < 0 && hd_wgrad_small_eligible(a)) {
-      hd_wgrad_small_launch(a, (hipStream_t)stream);
-      HD_CHECK_LAUNCH();
-      return HD_OK;
-    }
+  HD_CHECK_ARG(!a->in_scale || r.fam == WG_SMALL, "hd_wgrad: consumer-side BatchNorm (in_scale / in_shift) is implemented by the small-channel 3x3 kernel only "
+                                                  "(3x3 / stride 1 / pad 1, one source, C1 in {16,32}, Cout <= 32)");
+  HD_CHECK_ARG(!a->dw_oihw || (r.fam == WG_W8 && a->nsplit == 1), "hd_wgrad: dw_oihw (direct output) needs nsplit == 1 and the 8-wave 3x3 kernel (hd_wgrad_direct_ok)");
+  if (r.fam == WG_GENERAL) {
+    const int64_t xb = (int64_t)a->N * a->Hsrc * a->Wsrc * a->C1 * 2, x2b = a->x2 ? (int64_t)a->N * a->Hin * a->Win * a->C2 * 2 : 0;
+    const int64_t db = (int64_t)a->N * a->Ho * a->Wo * a->Cout * 2;
+    HD_CHECK_ARG(xb < 0xFFFFFFF0ll && x2b < 0xFFFFFFF0ll && db < 0xFFFFFFF0ll, "hd_wgrad: tensor larger than 4 GiB (buffer addressing)");
   }
-  HD_CHECK_ARG(!a->in_scale, "hd_wgrad: consumer-side BatchNorm (in_scale / in_shift) is implemented by the small-channel 3x3 kernel only "
-                             "(3x3 / stride 1 / pad 1, one source, C1 in {16,32}, Cout <= 32)");
-  {
-    static const char* env8 = getenv("HD_WGRAD_W8");
-    static const bool w8_on = !(env8 && env8[0] == '0');
-    if (w8_on && g_wg_tm < 0 && hd_wgrad_w8_eligible(a)) {
-      hd_wgrad_w8_launch(a, (hipStream_t)stream);
-      HD_CHECK_LAUNCH();
-      return HD_OK;
-    }
+  return HD_OK;
+}
+
+static void wg_launch(const hd_wgrad_args* a, const WgRoute& r, hipStream_t s) {
+  switch (r.fam) {
+    case WG_SMALL: case WG_SMALL_CAT: return hd_wgrad_small_launch(a, s);
+    case WG_W8: return hd_wgrad_w8_launch(a, s);
   }
   WgP p;
   p.x = (const f16*)a->x; p.x2 = (const f16*)a->x2; p.dy = (const f16*)a->dy; p.slab = a->slab;
   p.N = a->N; p.Hsrc = a->Hsrc; p.Wsrc = a->Wsrc; p.Hin = a->Hin; p.Win = a->Win; p.C1 = a->C1; p.C2 = a->C2;
   p.Cin = a->C1 + a->C2; p.Ho = a->Ho; p.Wo = a->Wo; p.Cout = a->Cout; p.KH = a->KH; p.KW = a->KW;
-  p.stride = a->stride; p.pad = a->pad; p.up1 = a->up1;
-  p.M = a->N * a->Ho * a->Wo;
-  p.cin8 = p.Cin / 8;
-  p.nchunks = a->KH * a->KW * p.cin8;
-  p.Ktot = a->KH * a->KW * p.Cin;
-  int per = hd_cdiv(p.M, a->nsplit);
-  per = hd_cdiv(per, BP) * BP;
-  p.per_split = per;
-  {
-    int64_t xb = (int64_t)a->N * a->Hsrc * a->Wsrc * a->C1 * 2, x2b = a->x2 ? (int64_t)a->N * a->Hin * a->Win * a->C2 * 2 : 0;
-    int64_t db = (int64_t)p.M * a->Cout * 2;
-    HD_CHECK_ARG(xb < 0xFFFFFFF0ll && x2b < 0xFFFFFFF0ll && db < 0xFFFFFFF0ll, "hd_wgrad: tensor larger than 4 GiB (buffer addressing)");
-    p.xbytes = (unsigned)xb; p.x2bytes = (unsigned)x2b; p.dybytes = (unsigned)db;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const int tm = g_wg_tm > 0 ? g_wg_tm : (p.Cout > 64 ? 128 : (p.Cout > 32 ? 64 : 32));
-  dim3 grid(hd_cdiv(p.Ktot, TN), hd_cdiv(p.Cout, tm), a->nsplit);
-  if (tm == 128) hipLaunchKernelGGL((wgrad_kernel<128, 2, 2>), grid, dim3(256), 0, s, p);
-  else if (tm == 64) hipLaunchKernelGGL((wgrad_kernel<64, 2, 2>), grid, dim3(256), 0, s, p);
+  p.stride = a->stride; p.pad = a->pad; p.up1 = a->up1; p.M = a->N * a->Ho * a->Wo;
+  p.cin8 = p.Cin / 8; p.nchunks = a->KH * a->KW * p.cin8; p.Ktot = a->KH * a->KW * p.Cin;
+  p.per_split = hd_cdiv(hd_cdiv(p.M, a->nsplit), BP) * BP;
+  p.xbytes = (unsigned)((int64_t)a->N * a->Hsrc * a->Wsrc * a->C1 * 2);       // < 4 GiB each: wg_accepts
+  p.x2bytes = a->x2 ? (unsigned)((int64_t)a->N * a->Hin * a->Win * a->C2 * 2) : 0u;
+  p.dybytes = (unsigned)((int64_t)p.M * a->Cout * 2);
+  dim3 grid(hd_cdiv(p.Ktot, TN), hd_cdiv(p.Cout, r.tm), a->nsplit);
+  if (r.tm == 128) hipLaunchKernelGGL((wgrad_kernel<128, 2, 2>), grid, dim3(256), 0, s, p);
+  else if (r.tm == 64) hipLaunchKernelGGL((wgrad_kernel<64, 2, 2>), grid, dim3(256), 0, s, p);
   else hipLaunchKernelGGL((wgrad_kernel<32, 1, 4>), grid, dim3(256), 0, s, p);
+}
+
+extern "C" int hd_wgrad(const hd_wgrad_args* a, void* stream) {
+  HD_CHECK_ARG(a, "hd_wgrad: null pointer");
+  const WgRoute r = wg_route(a);
+  const int rc = wg_accepts(a, r);
+  if (rc) return rc;
+  wg_launch(a, r, (hipStream_t)stream);
   HD_CHECK_LAUNCH();
   return HD_OK;
 }
 
-// n independent weight gradients; ONE grid when every entry runs in the 8-wave patch-staged kernel (wgrad3x3_w8.hip), else n launches
-void hd_wgrad_w8_launch_multi(const hd_wgrad_args* a, int n, hipStream_t s);
+// n independent weight gradients; ONE grid when every entry runs in the 8-wave patch-staged kernel (wgrad3x3_w8.hip), else n launches.
+// A refused entry refuses the call before anything is launched.
 extern "C" int hd_wgrad_multi(const hd_wgrad_args* args, int n, void* stream) {
   HD_CHECK_ARG(args && n > 0, "hd_wgrad_multi: bad args");
-  static const char* env = getenv("HD_WGRAD_MULTI");
-  bool one = !(env && env[0] == '0') && n >= 2 && n <= HD_WGRAD_MULTI_MAX;
-  for (int i = 0; i < n; ++i)
-    HD_CHECK_ARG(!args[i].dw_oihw || hd_wgrad_direct_ok(args + i), "hd_wgrad_multi: dw_oihw (direct output) needs nsplit == 1 and the 8-wave 3x3 kernel");
-  for (int i = 0; one && i < n; ++i) one = hd_wgrad_takes_w8(args + i);
-  if (!one) {
-    for (int i = 0; i < n; ++i) {
-      const int rc = hd_wgrad(args + i, stream);
-      if (rc) return rc;
-    }
+  bool one = wg_knobs().multi && n >= 2 && n <= HD_WGRAD_MULTI_MAX;
+  for (int i = 0; i < n; ++i) {
+    const WgRoute r = wg_route(args + i);
+    const int rc = wg_accepts(args + i, r);
+    if (rc) return rc;
+    one = one && r.fam == WG_W8;
+  }
+  if (one) {
+    hd_wgrad_w8_launch_multi(args, n, (hipStream_t)stream);
+    HD_CHECK_LAUNCH();
     return HD_OK;
   }
   for (int i = 0; i < n; ++i) {
-    const hd_wgrad_args* a = args + i;
-    HD_CHECK_ARG(a->C1 > 0 && a->C1 % 8 == 0 && a->C2 % 8 == 0 && a->Cout % 8 == 0 && (a->C2 == 0) == (a->x2 == nullptr) && a->nsplit >= 1,
-                 "hd_wgrad_multi: bad entry");
+    const int rc = hd_wgrad(args + i, stream);
+    if (rc) return rc;
   }
-  hd_wgrad_w8_launch_multi(args, n, (hipStream_t)stream);
-  HD_CHECK_LAUNCH();
+  return HD_OK;
+}
+
+// the queries: views of the route (hd_wgrad_route: include/hallucidet_hip.h has the layout of `out`)
+extern "C" int hd_wgrad_w8_blocks(const hd_wgrad_args* a) { return a && wg_route(a).fam == WG_W8 ? wg_route(a).wtiles : 0; }
+extern "C" int hd_wgrad_direct_ok(const hd_wgrad_args* a) { return a && a->nsplit == 1 && wg_route(a).fam == WG_W8; }
+
+extern "C" int hd_wgrad_route(const hd_wgrad_args* a, int32_t out[8]) {
+  HD_CHECK_ARG(a && out, "hd_wgrad_route: null pointer");
+  const WgRoute r = wg_route(a);
+  const int rc = wg_accepts(a, r);
+  if (rc) return rc;
+  const bool w8 = r.fam == WG_W8;
+  const int32_t v[8] = {r.fam, r.tm, r.wtiles, r.ptiles, w8 && a->nsplit == 1, w8, r.wtiles * a->nsplit, 0};
+  for (int i = 0; i < 8; ++i) out[i] = v[i];
   return HD_OK;
 }
 

@@ -6,6 +6,7 @@ include/hallucidet_hip.h, last section).  A parity mode, not a fast path.
 Nothing here computes on the host and nothing falls back to ATen: a missing library
 or a failing launch raises (``_abi.HipLibraryMissing`` / ``_abi.HipCallError``).
 """
+import collections
 import ctypes as C
 import os
 import threading
@@ -163,33 +164,17 @@ def wgrad(x, dy, KH, KW, *, x2=None, stride=1, pad=0, up1=False, nsplit=None, in
     hd_wgrad_direct_ok): the kernel writes dw = dw_scale * gradient itself (== wgrad_reduce of the one slab, bit for bit) and None is
     returned; where the kernel cannot, the slab is returned and the caller reduces as usual."""
     _need_cuda(x, dy, x2)
-    lib = _abi.load()
     N, Hs, Ws, C1 = x.shape
     C2 = 0 if x2 is None else x2.shape[3]
     _, Ho, Wo, Cout = dy.shape
     Hin, Win = (Hs * 2, Ws * 2) if up1 else (Hs, Ws)
     K = KH * KW * (C1 + C2)
-    M = N * Ho * Wo
-    if nsplit is None and x.dtype == torch.float32:
-        nsplit = pick_nsplit(M, Cout, K)
-    if nsplit is None:
-        probe = WgradArgs(ptr(x), ptr(x2), ptr(dy), None, N, Hs, Ws, Hin, Win, C1, C2, Ho, Wo, Cout, KH, KW, stride, pad, 1 if up1 else 0, 1)
-        blocks8 = lib.hd_wgrad_w8_blocks(C.byref(probe))
-        if blocks8 > 0:
-            # 8-wave patch kernel: one 512-thread block per CU, at least four 16x8-pixel tiles per block
-            tiles = N * ((Ho + 15) // 16) * ((Wo + 7) // 8)
-            nsplit = max(1, min(_WGRAD8_BLOCKS // blocks8, tiles // 4))
-            while nsplit > 1 and nsplit * Cout * K * 4 > (64 << 20):
-                nsplit //= 2
-        elif x2 is not None and up1 and KH == 3 and C1 == 64 and C2 == 64 and Cout <= 32 and stride == 1 and pad == 1:
-            nsplit = 256          # thin-output kernel on the decoder concat (wgrad3x3_small.hip): 125 KB of LDS, one persistent block per CU
-        else:
-            nsplit = pick_nsplit(M, Cout, K)
     direct = False
-    if dw is not None and nsplit == 1 and x.dtype == torch.float16:
-        probe = WgradArgs(ptr(x), ptr(x2), ptr(dy), None, N, Hs, Ws, Hin, Win, C1, C2, Ho, Wo, Cout, KH, KW, stride, pad, 1 if up1 else 0, 1,
-                          ptr(in_scale), ptr(in_shift), 1 if in_relu else 0, 0)
-        direct = lib.hd_wgrad_direct_ok(C.byref(probe)) == 1
+    if x.dtype == torch.float32:                  # parity mode: one kernel (hd_wgrad_f32), nothing to route
+        nsplit = nsplit or pick_nsplit(N * Ho * Wo, Cout, K)
+    elif nsplit is None or dw is not None:        # one question: which kernel runs, with which split, and does it write dw itself?
+        plan = wgrad_plan(N, Hs, Ws, C1, Ho, Wo, Cout, KH, KW, C2=C2, stride=stride, pad=pad, up1=up1, in_scale=in_scale is not None, nsplit=nsplit)
+        nsplit, direct = plan.nsplit, dw is not None and plan.direct
         if direct:
             assert dw.dtype == torch.float32 and dw.is_contiguous() and dw.numel() == Cout * K
     slab = None if direct else torch.empty((nsplit, Cout, K), dtype=torch.float32, device=x.device)
@@ -250,16 +235,40 @@ def conv2d_multi(calls):
 WGRAD_MULTI_MAX = 24      # HD_WGRAD_MULTI_MAX
 
 
+WGRAD_FAMILIES = ("general", "small", "small-cat", "w8")      # hd_wgrad_route's out[0]
+WgradPlan = collections.namedtuple("WgradPlan", "family tm weight_tiles pixel_tiles direct shared blocks nsplit")
+
+
+def wgrad_plan(N, Hs, Ws, C1, Ho, Wo, Cout, KH, KW, *, C2=0, stride=1, pad=0, up1=False, in_scale=False, nsplit=None, dw=False):
+    """What hd_wgrad (fp16 storage) does with a problem, from its shape alone -- no tensor, no GPU: the route hd_wgrad_route reports
+    (family name, the general kernel's Cout tile, weight tiles = blocks per pixel split, pixel tiles, dw honoured, shares the
+    hd_wgrad_multi / hd_conv2d_wgrad grid, blocks of the grid) and the pixel split: `nsplit` as given, else the default, which is keyed
+    on the family that runs.  `dw`: ask for the direct OIHW output.  Raises HipCallError where hd_wgrad refuses the block."""
+    P = 0x1000      # stands for every tensor pointer: the query follows none
+    Hin, Win = (Hs * 2, Ws * 2) if up1 else (Hs, Ws)
+    a = WgradArgs(P, P if C2 else None, P, P, N, Hs, Ws, Hin, Win, C1, C2, Ho, Wo, Cout, KH, KW, stride, pad, 1 if up1 else 0, nsplit or 1,
+                  P if in_scale else None, P if in_scale else None, 1, 0, P if dw else None, 1.0, 0)
+    r = (C.c_int32 * 8)()
+    check(_abi.load().hd_wgrad_route(C.byref(a), r), "hd_wgrad_route")
+    family, K = WGRAD_FAMILIES[r[0]], KH * KW * (C1 + C2)
+    if nsplit is None and family == "w8":
+        # one 512-thread block per CU, at least four pixel tiles per block
+        nsplit = max(1, min(_WGRAD8_BLOCKS // r[2], r[3] // 4))
+        while nsplit > 1 and nsplit * Cout * K * 4 > (64 << 20):
+            nsplit //= 2
+    elif nsplit is None and family == "small-cat":
+        nsplit = 256              # thin-output kernel on the decoder concat (wgrad3x3_small.hip): 125 KB of LDS, one persistent block per CU
+    elif nsplit is None:
+        nsplit = pick_nsplit(N * Ho * Wo, Cout, K)
+    return WgradPlan(family, r[1], r[2], r[3], bool(r[4]) and nsplit == 1, bool(r[5]), r[2] * nsplit, nsplit)
+
+
 def wgrad_w8_blocks(x, dy, KH, KW, *, x2=None, stride=1, pad=0, up1=False, **_):
-    """(Cin / 64) * (Cout / 64) if hd_wgrad routes this problem to the 8-wave patch-staged 3x3 kernel, else 0 (hd_wgrad_w8_blocks)."""
+    """(Cin / 64) * (Cout / 64) if hd_wgrad routes this problem to the 8-wave patch-staged 3x3 kernel, else 0."""
     if x.dtype != torch.float16:
         return 0
-    N, Hs, Ws, C1 = x.shape
-    C2 = 0 if x2 is None else x2.shape[3]
-    _, Ho, Wo, Cout = dy.shape
-    Hin, Win = (Hs * 2, Ws * 2) if up1 else (Hs, Ws)
-    probe = WgradArgs(ptr(x), ptr(x2), ptr(dy), None, N, Hs, Ws, Hin, Win, C1, C2, Ho, Wo, Cout, KH, KW, stride, pad, 1 if up1 else 0, 1)
-    return int(_abi.load().hd_wgrad_w8_blocks(C.byref(probe)))
+    p = wgrad_plan(*x.shape, *dy.shape[1:], KH, KW, C2=0 if x2 is None else x2.shape[3], stride=stride, pad=pad, up1=up1, nsplit=1)
+    return p.weight_tiles if p.family == "w8" else 0
 
 
 def wgrad_takes_w8(x, dy, KH, KW, **kw):

@@ -732,8 +732,7 @@ class UnetRunner:
                 # grid (ops.wgrad_multi): a block per 64 x 64 weight tile and LAYER walks that layer's pixel tiles and writes one 147 KB
                 # partial, where 256 blocks per layer wrote 256 -- 1 / 16 ... 1 / 256 of the slab bytes, the per-block fixed cost once.
                 dx = ops.conv2d(dy, wd, u.k, u.k, **dkw)
-                ns = self._wg_plan[u.name]
-                tiles = dy.shape[0] * ((dy.shape[1] + 15) // 16) * ((dy.shape[2] + 7) // 8)
+                ns, tiles = self._wg_plan[u.name]
                 self._wg_ready.append(((u, xt, dy, wkw, inv), ns, (tiles + ns - 1) // ns))
                 return dx, dres, (bstat["part"] if bstat is not None else None)
             slab, dx = ops.wgrad_dgrad(xt, dy, u.k, u.k, wd, dgrad=dkw, **wkw)
@@ -743,7 +742,7 @@ class UnetRunner:
         return dx, dres, (bstat["part"] if bstat is not None else None)
 
     def _plan_wgrads(self):
-        """{unit name: pixel split} for every convolution whose weight gradient the backward pass defers (3x3 / stride 1, >= 64 channels on
+        """{unit name: (pixel split, pixel tiles)} for every convolution whose weight gradient the backward pass defers (3x3 / stride 1, >= 64 channels on
         both sides, materialised operand: the 8-wave kernel's domain), from the saved forward record -- BEFORE the pass, for the two launch
         groups (segments 0-2: decoder, layer4, layer3; segments 3-4: layer2, layer1) as whole grids, so that a layer's split, and with it
         the rounding of its gradient, is the same whether the groups are launched whole (no exchange hook) or segment by segment."""
@@ -771,13 +770,13 @@ class UnetRunner:
             for k, u, r, xt in cand:
                 if k not in group:
                     continue
-                y = r["y"]
-                b = ops.wgrad_w8_blocks(xt, y, u.k, u.k, x2=r["x2"], stride=u.stride, pad=u.pad, up1=r["up1"])
-                if b > 0:
+                p = ops.wgrad_plan(*xt.shape, *r["y"].shape[1:], u.k, u.k, C2=0 if r["x2"] is None else r["x2"].shape[3], stride=u.stride, pad=u.pad,
+                                   up1=bool(r["up1"]), nsplit=1)
+                if p.family == "w8":
                     names.append(u.name)
-                    geo.append((b, y.shape[0] * ((y.shape[1] + 15) // 16) * ((y.shape[2] + 7) // 8)))
+                    geo.append((p.weight_tiles, p.pixel_tiles))
             if names:
-                plan.update(zip(names, _plan_wgrad_splits(geo)))
+                plan.update(zip(names, zip(_plan_wgrad_splits(geo), (t for _, t in geo))))
         if len(cache) >= 8:
             cache.pop(next(iter(cache)))
         cache[key] = plan

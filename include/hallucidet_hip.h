@@ -202,6 +202,19 @@ int hd_wgrad_multi(const hd_wgrad_args* args, int n, void* stream);
 /* blocks per pixel slice the 8-wave 3x3 weight-gradient kernel uses for this problem ((Cin/64) * (Cout/64)), 0 if hd_wgrad
  * will not route it there: lets the caller choose `nsplit` so that nsplit * blocks fills the GPU */
 int hd_wgrad_w8_blocks(const hd_wgrad_args* a);
+/* Read-only: which kernel hd_wgrad would launch for this argument block (the same routing decision, no launch, no HIP call, no pointer
+ * followed; hd_wgrad_direct_ok and hd_wgrad_w8_blocks are views of it).
+ *   out[0] family: 0 general implicit GEMM, 1 small-channel 3x3 (C1 in {16,32}, Cout <= 32), 2 the same kernel on the decoder concat
+ *          (64 upsampled + 64 skip channels), 3 8-wave patch-staged 3x3
+ *   out[1] family 0: the Cout tile (32 / 64 / 128 rows); others 0
+ *   out[2] weight tiles = thread blocks per pixel split (0: 128-column x out[1]-row tiles; 1, 2: 1; 3: (Cin / 64) * (Cout / 64))
+ *   out[3] pixel tiles the splits share (0: 32-pixel reduction tiles; 1, 2: 8 x 32-pixel tiles; 3: N * ceil(Ho / 16) * ceil(Wo / 8))
+ *   out[4] 1 = dw_oihw is honoured for this block (family 3 and nsplit == 1)
+ *   out[5] 1 = the block shares the single grid of hd_wgrad_multi / hd_conv2d_wgrad (family 3)
+ *   out[6] thread blocks of the grid as launched with args->nsplit (out[2] * nsplit)
+ *   out[7] 0
+ * Returns HD_OK, or HD_E_ARG for an argument block hd_wgrad would refuse. */
+int hd_wgrad_route(const hd_wgrad_args* a, int32_t out[8]);
 /* tuning hook (tools/tune_wgrad.py): force hd_wgrad's Cout tile (32 / 64 / 128 rows); -1 = by channel count. Process-wide. */
 int hd_wgrad_tune_override(int tm);
 /* n independent hd_conv2d problems (an array of argument blocks) as ONE grid where they all run in the same 4-wave implicit-GEMM

@@ -59,14 +59,14 @@ def conv2d_dgrad_nhwc(dy, w_flat, KH, KW, cin, *, stride, pad, in_hw):
     return nchw_to_nhwc(dx)
 
 
-def conv2d_wgrad_nhwc(x, dy, KH, KW, *, x2=None, stride=1, pad=0, up1=False):
-    """Weight gradient in [Cout, KH*KW*Cin] (kh,kw,ci) order, fp32."""
-    xi = nhwc_to_nchw(x.float())
+def conv2d_wgrad_nhwc(x, dy, KH, KW, *, x2=None, stride=1, pad=0, up1=False, dtype=torch.float32):
+    """Weight gradient in [Cout, KH*KW*Cin] (kh,kw,ci) order, computed in `dtype` (fp32, or fp64 for a reference free of summation error)."""
+    xi = nhwc_to_nchw(x.to(dtype))
     if up1:
         xi = upsample_deterministic(xi, 2)
     if x2 is not None:
-        xi = torch.cat([xi, nhwc_to_nchw(x2.float())], dim=1)
-    g = nhwc_to_nchw(dy.float())
+        xi = torch.cat([xi, nhwc_to_nchw(x2.to(dtype))], dim=1)
+    g = nhwc_to_nchw(dy.to(dtype))
     cout, cin = g.shape[1], xi.shape[1]
     dw = torch.nn.grad.conv2d_weight(xi, (cout, cin, KH, KW), g, stride=stride, padding=pad)
     return dw.permute(0, 2, 3, 1).reshape(cout, KH * KW * cin)

@@ -1462,6 +1462,68 @@ def test_wgrad_multi_is_bit_identical_to_separate_launches_and_direct_output_to_
         ops.check(_abi.load().hd_wgrad(C.byref(a), None), "hd_wgrad")
 
 
+WGRAD_PLAN_CASES = [
+    # family, x, x2, dy, K, pad, up1, in_scale
+    ("small", (1, 8, 8, 16), None, (1, 8, 8, 16), 3, 1, False, False),
+    ("small", (1, 8, 8, 16), None, (1, 8, 8, 16), 3, 1, False, True),
+    ("small-cat", (1, 4, 4, 64), (1, 8, 8, 64), (1, 8, 8, 32), 3, 1, True, False),
+    ("w8", (1, 32, 32, 64), None, (1, 32, 32, 64), 3, 1, False, False),          # eight 16 x 8-pixel tiles: default split 2
+    ("general", (2, 9, 7, 24), None, (2, 9, 7, 40), 1, 0, False, False),
+]
+
+
+@pytest.mark.parametrize("case", WGRAD_PLAN_CASES, ids=lambda c: c[0] + ("-in_scale" if c[7] else ""))
+def test_the_wgrad_plan_is_what_runs(dev, case):
+    """One problem per kernel family: ops.wgrad without nsplit returns the slab of ops.wgrad_plan's split, bit for bit what the explicit
+    split gives, and its sum is the weight gradient (fp64 reference, test_conv2d_wgrad's tolerance)."""
+    from hallucidet_amd import ops
+    family, xs, x2s, dys, K, pad, up1, raw = case
+    x, dy = rnd(*xs, seed=31), rnd(*dys, seed=33)
+    x2 = rnd(*x2s, seed=32) if x2s else None
+    d = lambda t: None if t is None else t.to(dev)
+    kw = dict(x2=d(x2), pad=pad, up1=up1)
+    xin = x
+    if raw:                                      # x is a raw conv output: the kernel reads relu(fp16(x * scale + shift)) in its place
+        scale, shift = (torch.rand(xs[3]) + 0.5).to(dev), (torch.randn(xs[3]) * 0.1).to(dev)
+        kw.update(in_scale=scale, in_shift=shift)
+        xin = ops.bn_apply(d(x), scale, shift, relu=True).cpu()
+    plan = ops.wgrad_plan(*xs, *dys[1:], K, K, C2=x2s[3] if x2s else 0, pad=pad, up1=up1, in_scale=raw)
+    assert plan.family == family and (family != "w8" or plan.nsplit == 2)
+    slab = ops.wgrad(d(x), d(dy), K, K, **kw)
+    assert slab.shape == (plan.nsplit, dys[3], K * K * (xs[3] + (x2s[3] if x2s else 0)))
+    assert torch.equal(slab, ops.wgrad(d(x), d(dy), K, K, nsplit=plan.nsplit, **kw))
+    want = ok.conv2d_wgrad_nhwc(xin, dy, K, K, x2=x2, pad=pad, up1=up1, dtype=torch.float64)
+    close(slab.double().sum(dim=0).cpu(), want, rtol=2e-3, atol=2e-3 * math.sqrt(dys[0] * dys[1] * dys[2]))
+
+
+def test_the_wgrad_tile_override_is_honoured_by_every_caller(dev):
+    """hd_wgrad_tune_override on an 8-wave shape: the plan says general kernel and no direct output, and ops.wgrad (dw given), ops.wgrad_multi
+    and ops.wgrad_dgrad all act on that answer -- a slab comes back, dw stays untouched, and the grouped calls equal the separate ones."""
+    from hallucidet_amd import _abi, ops
+    lib = _abi.load()
+    x, dy, xb, dyb, wd = (rnd(1, 32, 32, 64, seed=s).to(dev) for s in (41, 42, 43, 44, 45))
+    wd = wd.reshape(-1)[:64 * 9 * 64].reshape(64, 9 * 64).contiguous()
+    shape = (1, 32, 32, 64, 32, 32, 64, 3, 3)
+    assert ops.wgrad_plan(*shape, pad=1, nsplit=1).direct
+    try:
+        ops.check(lib.hd_wgrad_tune_override(64), "hd_wgrad_tune_override")
+        plan = ops.wgrad_plan(*shape, pad=1, nsplit=1)
+        assert (plan.family, plan.tm, plan.direct, plan.shared) == ("general", 64, False, False)
+        assert ops.wgrad_w8_blocks(x, dy, 3, 3, pad=1) == 0
+        dw = torch.full((64, 64, 3, 3), 7.0, device=dev)
+        slab = ops.wgrad(x, dy, 3, 3, pad=1, nsplit=1, dw=dw)
+        assert slab is not None and slab.shape == (1, 64, 576) and bool((dw == 7.0).all())
+        calls = [(x, dy, 3, 3, dict(pad=1, nsplit=1, dw=dw)), (xb, dyb, 3, 3, dict(pad=1, nsplit=2))]
+        outs = ops.wgrad_multi(calls)
+        assert torch.equal(outs[0], slab) and torch.equal(outs[1], ops.wgrad(xb, dyb, 3, 3, pad=1, nsplit=2)) and bool((dw == 7.0).all())
+        s2, dx = ops.wgrad_dgrad(x, dy, 3, 3, wd, pad=1, dgrad=dict(pad=1, cout=64))
+        assert torch.equal(s2, ops.wgrad(x, dy, 3, 3, pad=1)) and torch.equal(dx, ops.conv2d(dy, wd, 3, 3, pad=1, cout=64))
+        assert s2.shape[0] == ops.wgrad_plan(*shape, pad=1).nsplit
+    finally:
+        lib.hd_wgrad_tune_override(-1)
+    assert ops.wgrad(x, dy, 3, 3, pad=1, nsplit=1, dw=dw) is None and not bool((dw == 7.0).any())
+
+
 def test_small_grid_conv_is_batch_invariant_and_run_to_run_identical(dev):
     """Image n of a batched launch equals the same image alone, and two runs agree, bit for bit, on a small-grid long-K layer (the
     property an in-launch split-K must keep; a ticketed split-K of the 64-deep family was built against this test, measured
