@@ -243,6 +243,62 @@ def _active_views(feats, n_active):
     return None
 
 
+class _Packed:
+    """Mixin of the modules that run from a derived weight pack (fp16 GEMM layouts, folded FrozenBN): `pack()` builds it on first use
+    (`_build_pack`), `invalidate()` drops it after the parameters changed.  `train_params` / `grad_scale` (set by `set_trainable`): the
+    backward also accumulates parameter gradients, with the loss scale removed.  Registers no parameter, buffer or submodule."""
+    _pack = None
+    train_params, grad_scale = False, 1.0
+
+    def invalidate(self):
+        self._pack = None
+
+    def pack(self):
+        if self._pack is None:
+            self._pack = self._build_pack()
+        return self._pack
+
+
+class _PyramidHead(_Packed):
+    """A head that runs on every pyramid level through one autograd Function `_Fn(hook, head, n_active, nlev, *feats, *acts)`:
+    RPNHead, RetinaNetHead, FCOSHead.  The Function enters through `_head_enter` and leaves through `_head_exit`."""
+    _hook = None          # a leaf that requires grad: the Function runs its backward (parameter gradients) whatever the features require
+    _Fn = None
+
+    def _run(self, feats, n_active=None):
+        feats = list(feats)
+        if self._hook is None or self._hook.device != feats[0].device:
+            self._hook = torch.zeros(1, device=feats[0].device, requires_grad=True)
+        na = feats[0].shape[0] if n_active is None else n_active
+        acts = _active_views(feats, na) if na < feats[0].shape[0] else None
+        return self._Fn.apply(self._hook, self, na, len(feats), *feats, *(acts or ()))
+
+
+def _head_enter(ctx, head, n_active, nlev, feats):
+    """Entry of a pyramid-head Function -> the `nlev` full feature maps.  `has_acts`: the [n_active] views of `_active_views` follow
+    them in `feats`; autograd differentiates those, and the gradients leave with n_active rows."""
+    ctx.has_acts = len(feats) > nlev
+    ctx.set_materialize_grads(False)          # unused outputs arrive as None in backward, not as zero-filled maps
+    feats = feats[:nlev]
+    ctx.head, ctx.na, ctx.n = head, n_active, feats[0].shape[0]
+    return feats
+
+
+def _head_exit(ctx, dfeats):
+    """Exit of a pyramid-head Function's backward.  dfeats: one [n_active, ...] gradient (or None) per level.  Without active views
+    the gradients belong to the full [n] maps: the Function pads them with zero rows, here and nowhere else."""
+    if ctx.na < ctx.n and not ctx.has_acts:
+        padded = []
+        for df in dfeats:
+            if df is not None:
+                full = torch.zeros((ctx.n,) + tuple(df.shape[1:]), dtype=df.dtype, device=df.device)
+                full[:ctx.na] = df
+                df = full
+            padded.append(df)
+        dfeats = padded
+    return (None,) * (4 + (len(dfeats) if ctx.has_acts else 0)) + tuple(dfeats)
+
+
 class _BackboneFn(torch.autograd.Function):
     """`n_active`: only the first n_active images of the batch need a data gradient (the hallucinated images when the
     RGB / IR detector passes of a training step are batched with them); the rest is forward-only."""
@@ -293,7 +349,7 @@ class _BackboneFn(torch.autograd.Function):
         return dx, None, None, None
 
 
-class BackboneWithFPN(nn.Module):
+class BackboneWithFPN(_Packed, nn.Module):
     out_channels = 256
 
     def __init__(self, returned_layers=(1, 2, 3, 4), extra_blocks=None):
@@ -307,17 +363,10 @@ class BackboneWithFPN(nn.Module):
         self.fpn = FeaturePyramidNetwork(chans, 256, extra_blocks)
         self.p6p7 = isinstance(self.fpn.extra_blocks, LastLevelP6P7)
         self.out_names = tuple(str(i) for i in range(len(chans))) + (("p6", "p7") if self.p6p7 else ("pool",))
-        self._pack = None
         self._hook = None
-        self.train_params, self.grad_scale = False, 1.0     # set by FasterRCNN.set_trainable (detector fine-tuning)
 
     # -------------------------------------------------------------- frozen weight pack
-    def invalidate(self):
-        self._pack = None
-
-    def pack(self):
-        if self._pack is not None:
-            return self._pack
+    def _build_pack(self):
         b = self.body
         P = {"stem": _conv_entry(b.conv1, b.bn1, cin_pad=8), "blocks": [], "inner": [], "layer": []}
         for li in range(1, 5):
@@ -332,7 +381,6 @@ class BackboneWithFPN(nn.Module):
             P["layer"].append(_conv_entry(c))
         if self.p6p7:
             P["p6"], P["p7"] = _conv_entry(self.fpn.extra_blocks.p6), _conv_entry(self.fpn.extra_blocks.p7)
-        self._pack = P
         return P
 
     # -------------------------------------------------------------- execution
@@ -726,9 +774,7 @@ class AnchorGenerator(nn.Module):
 class _RPNHeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, hook, head, n_active, nlev, *feats):
-        ctx.has_acts = len(feats) > nlev
-        ctx.set_materialize_grads(False)
-        feats = feats[:nlev]
+        feats = _head_enter(ctx, head, n_active, nlev, feats)
         P = head.pack()
         nl = len(feats)
         tfull = _fwd_many([P["conv"]] * nl, feats, act=ACT_RELU)
@@ -738,7 +784,7 @@ class _RPNHeadFn(torch.autograd.Function):
         for li in range(nl):
             outs.append(heads[li])
             outs.append(heads[nl + li])
-        ctx.head, ctx.ts, ctx.na, ctx.n = head, ts, n_active, feats[0].shape[0]
+        ctx.ts = ts
         ctx.feats = [f[:n_active] for f in feats] if head.train_params else None
         return tuple(outs)
 
@@ -759,9 +805,7 @@ class _RPNHeadFn(torch.autograd.Function):
             dts = _dgrad_many([P["box"]] * nl, grs, hws, ress=dts, masks=list(ctx.ts))
             dfeats = _dgrad_many([P["conv"]] * nl, dts, hws)
             ctx.ts = None
-            if ctx.has_acts:
-                return (None, None, None, None) + (None,) * len(dfeats) + tuple(dfeats)
-            return (None, None, None, None) + tuple(dfeats)
+            return _head_exit(ctx, dfeats)
         for i, t in enumerate(ctx.ts):
             N, H, W, _ = t.shape
             dl, dr = grads[2 * i], grads[2 * i + 1]
@@ -787,19 +831,14 @@ class _RPNHeadFn(torch.autograd.Function):
             if tp and dt is not None:
                 _wgrad_into(ctx.head.conv.weight, P["conv"], ctx.feats[i], dt, inv)
                 _bgrad_into(ctx.head.conv.bias, dt, inv)
-            df = None if dt is None else _dgrad(P["conv"], dt, hw)
-            if df is not None and na < ctx.n and not ctx.has_acts:
-                full = torch.zeros((ctx.n,) + tuple(df.shape[1:]), dtype=df.dtype, device=df.device)
-                full[:na] = df
-                df = full
-            dfeats.append(df)
+            dfeats.append(None if dt is None else _dgrad(P["conv"], dt, hw))
         ctx.ts = None
-        if ctx.has_acts:
-            return (None, None, None, None) + (None,) * len(dfeats) + tuple(dfeats)
-        return (None, None, None, None) + tuple(dfeats)
+        return _head_exit(ctx, dfeats)
 
 
-class RPNHead(nn.Module):
+class RPNHead(_PyramidHead, nn.Module):
+    _Fn = _RPNHeadFn
+
     def __init__(self, in_channels=256, num_anchors=3):
         super().__init__()
         self.conv = nn.Conv2d(in_channels, in_channels, 3, padding=1)
@@ -808,25 +847,13 @@ class RPNHead(nn.Module):
         for layer in self.children():
             nn.init.normal_(layer.weight, std=0.01)
             nn.init.constant_(layer.bias, 0)
-        self._pack, self._hook = None, None
-        self.train_params, self.grad_scale = False, 1.0
 
-    def invalidate(self):
-        self._pack = None
-
-    def pack(self):
-        if self._pack is None:
-            self._pack = dict(conv=_conv_entry(self.conv), cls=_conv_entry(self.cls_logits), box=_conv_entry(self.bbox_pred))
-        return self._pack
+    def _build_pack(self):
+        return dict(conv=_conv_entry(self.conv), cls=_conv_entry(self.cls_logits), box=_conv_entry(self.bbox_pred))
 
     def forward(self, x, n_active=None):
         """x: list of NHWC fp16 feature maps.  Returns (logits, bbox_reg): lists of NCHW fp32 tensors per level."""
-        feats = list(x)
-        if self._hook is None or self._hook.device != feats[0].device:
-            self._hook = torch.zeros(1, device=feats[0].device, requires_grad=True)
-        na = feats[0].shape[0] if n_active is None else n_active
-        acts = _active_views(feats, na) if na < feats[0].shape[0] else None
-        outs = _RPNHeadFn.apply(self._hook, self, na, len(feats), *feats, *(acts or ()))
+        outs = self._run(x, n_active)
         return list(outs[0::2]), list(outs[1::2])
 
 
@@ -1026,31 +1053,24 @@ class _MLPFn(torch.autograd.Function):
         return dx, None
 
 
-class TwoMLPHead(nn.Module):
+class TwoMLPHead(_Packed, nn.Module):
     def __init__(self, in_channels=256 * 7 * 7, representation_size=1024):
         super().__init__()
         self.fc6 = nn.Linear(in_channels, representation_size)
         self.fc7 = nn.Linear(representation_size, representation_size)
-        self._pack = None
-        self.train_params, self.grad_scale = False, 1.0
 
-    def invalidate(self):
-        self._pack = None
-
-    def pack(self):
-        if self._pack is None:
-            rep, K = self.fc6.weight.shape
-            c = K // 49
-            w6 = self.fc6.weight.detach().float().view(rep, c, 7, 7)
-            e6 = dict(k=7, stride=1, pad=0, cin=c, cout=rep, cin_p=c, cout_p=rep, bias=self.fc6.bias.detach().float().contiguous())
-            e6["wf"], _ = ops.weight_prep(w6, cin_pad=c, cout_pad=rep, want_fwd=True, want_dgrad=False)
-            e6["wd"] = None
-            fc6_t = w6.permute(2, 3, 1, 0).reshape(49 * c, rep).to(e6["wf"].dtype).contiguous()
-            w7 = self.fc7.weight.detach().float().view(rep, rep, 1, 1)
-            e7 = dict(k=1, stride=1, pad=0, cin=rep, cout=rep, cin_p=rep, cout_p=rep, bias=self.fc7.bias.detach().float().contiguous())
-            e7["wf"], e7["wd"] = ops.weight_prep(w7, want_fwd=True, want_dgrad=True)
-            self._pack = dict(fc6=e6, fc7=e7, fc6_t=fc6_t)
-        return self._pack
+    def _build_pack(self):
+        rep, K = self.fc6.weight.shape
+        c = K // 49
+        w6 = self.fc6.weight.detach().float().view(rep, c, 7, 7)
+        e6 = dict(k=7, stride=1, pad=0, cin=c, cout=rep, cin_p=c, cout_p=rep, bias=self.fc6.bias.detach().float().contiguous())
+        e6["wf"], _ = ops.weight_prep(w6, cin_pad=c, cout_pad=rep, want_fwd=True, want_dgrad=False)
+        e6["wd"] = None
+        fc6_t = w6.permute(2, 3, 1, 0).reshape(49 * c, rep).to(e6["wf"].dtype).contiguous()
+        w7 = self.fc7.weight.detach().float().view(rep, rep, 1, 1)
+        e7 = dict(k=1, stride=1, pad=0, cin=rep, cout=rep, cin_p=rep, cout_p=rep, bias=self.fc7.bias.detach().float().contiguous())
+        e7["wf"], e7["wd"] = ops.weight_prep(w7, want_fwd=True, want_dgrad=True)
+        return dict(fc6=e6, fc7=e7, fc6_t=fc6_t)
 
     def forward(self, x):
         """x: [R,7,7,C] fp16 (RoIAlign output).  Returns [R,1,1,rep] fp16."""
@@ -1095,26 +1115,19 @@ class _PredictorFn(torch.autograd.Function):
         return dx, None
 
 
-class FastRCNNPredictor(nn.Module):
+class FastRCNNPredictor(_Packed, nn.Module):
     def __init__(self, in_channels, num_classes):
         super().__init__()
         self.cls_score = nn.Linear(in_channels, num_classes)
         self.bbox_pred = nn.Linear(in_channels, num_classes * 4)
-        self._pack = None
-        self.train_params, self.grad_scale = False, 1.0
 
-    def invalidate(self):
-        self._pack = None
-
-    def pack(self):
-        if self._pack is None:
-            def ent(lin):
-                o, i = lin.weight.shape
-                e = dict(k=1, stride=1, pad=0, cin=i, cout=o, cin_p=i, cout_p=(o + 7) // 8 * 8, bias=lin.bias.detach().float().contiguous())
-                e["wf"], e["wd"] = ops.weight_prep(lin.weight.detach().float().view(o, i, 1, 1), cout_pad=e["cout_p"], want_fwd=True, want_dgrad=True)
-                return e
-            self._pack = dict(cls=ent(self.cls_score), box=ent(self.bbox_pred))
-        return self._pack
+    def _build_pack(self):
+        def ent(lin):
+            o, i = lin.weight.shape
+            e = dict(k=1, stride=1, pad=0, cin=i, cout=o, cin_p=i, cout_p=(o + 7) // 8 * 8, bias=lin.bias.detach().float().contiguous())
+            e["wf"], e["wd"] = ops.weight_prep(lin.weight.detach().float().view(o, i, 1, 1), cout_pad=e["cout_p"], want_fwd=True, want_dgrad=True)
+            return e
+        return dict(cls=ent(self.cls_score), box=ent(self.bbox_pred))
 
     def forward(self, x):
         """x: [R,1,1,1024] fp16.  Returns fp32 (scores [R,K], bbox_deltas [R,4K])."""
@@ -1226,7 +1239,72 @@ class RoIHeads(nn.Module):
 # ======================================================================================================================
 # model
 # ======================================================================================================================
-class FasterRCNN(nn.Module):
+class _DetectorBase(nn.Module):
+    """What FasterRCNN, RetinaNet and FCOS share around their weight packs, detector fine-tuning and torchvision checkpoints.  A
+    detector declares `_packed()` (the modules that carry a pack and `train_params`), `_trainable()` (the modules whose parameters
+    train besides body.layer2-4), `_fpn_levels` and, optionally, `_rewrite_key` (one more torchvision >= 0.13 key rename).
+    Registers nothing: every detector registers its submodules itself, in torchvision's order (the state_dict key order)."""
+    _fpn_levels = 3
+    _rewrite_key = None
+
+    def invalidate_packs(self):
+        for m in self._packed():
+            m.invalidate()
+
+    def set_trainable(self, flag=True, grad_scale=1.0):
+        """Detector fine-tuning switch (train_detector.py / `train_det=True`): the hand-written backward chains also emit parameter
+        gradients (into `param.grad`), for what torchvision's *_resnet50_fpn factories leave trainable (trainable_backbone_layers=3
+        [EXT]: body.layer2-4 convs, the FPN with its extra blocks and every head; FrozenBN, conv1 and layer1 stay fixed)."""
+        for m in self._packed():
+            m.train_params, m.grad_scale = bool(flag), float(grad_scale)
+        for name, p in self.backbone.body.named_parameters():
+            p.requires_grad_(bool(flag) and name.split(".")[0] in ("layer2", "layer3", "layer4"))
+        for mod in self._trainable():
+            for p in mod.parameters():
+                p.requires_grad_(bool(flag))
+
+    def trainable_parameters(self):
+        return [p for p in self.parameters() if p.requires_grad]
+
+    @classmethod
+    def remap_state_dict_keys(cls, state_dict):
+        """torchvision >= 0.13 key names -> the 0.12 names this package (and the reference's checkpoints) use: the FPN
+        convs are wrapped in Conv2dNormActivation there, and so is what `_rewrite_key` renames."""
+        sd = OrderedDict()
+        for k, v in state_dict.items():
+            for i in range(cls._fpn_levels):
+                k = k.replace("fpn.inner_blocks.%d.0." % i, "fpn.inner_blocks.%d." % i).replace("fpn.layer_blocks.%d.0." % i, "fpn.layer_blocks.%d." % i)
+            if cls._rewrite_key is not None:
+                k = cls._rewrite_key(k)
+            if k.endswith("num_batches_tracked"):
+                continue
+            sd[k] = v
+        return sd
+
+    def load_state_dict(self, state_dict, strict=True):
+        out = super().load_state_dict(self.remap_state_dict_keys(state_dict), strict=strict)
+        self.invalidate_packs()
+        return out
+
+    def _apply(self, fn, *a, **k):
+        # .to() / .half() / .cuda() replace the parameters the packs were derived from.  Invalidating after the move (before it
+        # is as safe: nothing rebuilds a pack in between) so that the packs are dropped next to the line that made them stale.
+        out = super()._apply(fn, *a, **k)
+        self.invalidate_packs()
+        return out
+
+
+def _load_local_weights(model, weights_path):
+    """The factories' one source of weights: a local torchvision state_dict (nothing can be downloaded)."""
+    if weights_path is not None:
+        model.load_state_dict(torch.load(weights_path, map_location="cpu"))
+    return model
+
+
+class FasterRCNN(_DetectorBase):
+    _fpn_levels = 4
+    _rewrite_key = staticmethod(lambda k: k.replace("rpn.head.conv.0.0.", "rpn.head.conv."))
+
     def __init__(self, num_classes=91, min_size=800, max_size=1333):
         super().__init__()
         # torchvision's GeneralizedRCNNTransform is always replaced by the reference (detector.py:43-48); build that one.
@@ -1238,60 +1316,18 @@ class FasterRCNN(nn.Module):
         # True: eval_forward_fasterrcnn uses the batched/padded forms of the per-image loops (identical results)
         self.batched_heads = True
 
-    def invalidate_packs(self):
-        self.backbone.invalidate()
-        self.rpn.head.invalidate()
-        self.roi_heads.box_head.invalidate()
-        self.roi_heads.box_predictor.invalidate()
+    def _packed(self):
+        return (self.backbone, self.rpn.head, self.roi_heads.box_head, self.roi_heads.box_predictor)
 
-    def set_trainable(self, flag=True, grad_scale=1.0):
-        """Detector fine-tuning switch (train_detector.py / `train_det=True`): the hand-written backward chains also emit
-        parameter gradients (into `param.grad`), for what torchvision's fasterrcnn_resnet50_fpn leaves trainable
-        (trainable_backbone_layers=3 [EXT]: body.layer2-4 convs, FPN, RPN head, box head, predictor; FrozenBN, conv1 and
-        layer1 stay fixed)."""
-        for m in (self.backbone, self.rpn.head, self.roi_heads.box_head, self.roi_heads.box_predictor):
-            m.train_params, m.grad_scale = bool(flag), float(grad_scale)
-        for name, p in self.backbone.body.named_parameters():
-            p.requires_grad_(bool(flag) and name.split(".")[0] in ("layer2", "layer3", "layer4"))
-        for mod in (self.backbone.fpn, self.rpn, self.roi_heads):
-            for p in mod.parameters():
-                p.requires_grad_(bool(flag))
-
-    def trainable_parameters(self):
-        return [p for p in self.parameters() if p.requires_grad]
-
-    @staticmethod
-    def remap_state_dict_keys(state_dict):
-        """torchvision >= 0.13 key names -> the 0.12 names this module (and the reference's checkpoints) use."""
-        sd = OrderedDict()
-        for k, v in state_dict.items():
-            for i in range(4):
-                k = k.replace("fpn.inner_blocks.%d.0." % i, "fpn.inner_blocks.%d." % i).replace("fpn.layer_blocks.%d.0." % i, "fpn.layer_blocks.%d." % i)
-            k = k.replace("rpn.head.conv.0.0.", "rpn.head.conv.")
-            if k.endswith("num_batches_tracked"):
-                continue
-            sd[k] = v
-        return sd
-
-    def load_state_dict(self, state_dict, strict=True):
-        sd = self.remap_state_dict_keys(state_dict)
-        out = super().load_state_dict(sd, strict=strict)
-        self.invalidate_packs()
-        return out
-
-    def _apply(self, fn, *a, **k):
-        self.invalidate_packs()
-        return super()._apply(fn, *a, **k)
+    def _trainable(self):
+        return (self.backbone.fpn, self.rpn, self.roi_heads)
 
 
 def fasterrcnn_resnet50_fpn(pretrained=False, progress=True, num_classes=91, pretrained_backbone=False, weights_path=None, **kwargs):
     """torchvision.models.detection.fasterrcnn_resnet50_fpn [EXT].  COCO weights cannot be downloaded offline
     (SURVEY App. D.8): `pretrained=True` is accepted for signature compatibility and ignored unless `weights_path`
     points at a local torchvision state_dict."""
-    model = FasterRCNN(num_classes=num_classes)
-    if weights_path is not None:
-        model.load_state_dict(torch.load(weights_path, map_location="cpu"))
-    return model
+    return _load_local_weights(FasterRCNN(num_classes=num_classes), weights_path)
 
 
 # ======================================================================================================================

@@ -15,7 +15,6 @@ affines).  Target assignment (hd_fcos_match), the three losses (hd_fcos_loss / _
 of the post-processing are batched fp32 tensor ops on the GPU.  There is no CPU path.
 """
 import math
-from collections import OrderedDict
 
 import torch
 import torch.nn as nn
@@ -23,6 +22,7 @@ import torch.nn as nn
 from .. import ops
 from . import detection as D
 from .detection import _conv_entry, _dgrad, _fwd
+from .one_stage import OneStageDetector
 
 
 class BoxLinearCoder:
@@ -57,9 +57,7 @@ class _HeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, hook, head, n_active, nlev, *feats):
-        ctx.has_acts = len(feats) > nlev        # the [n_active] views the gradients are returned for (detection._active_views)
-        ctx.set_materialize_grads(False)          # unused outputs arrive as None in backward, not as zero-filled maps
-        feats = feats[:nlev]
+        feats = D._head_enter(ctx, head, n_active, nlev, feats)
         P = head.pack()
         # the 3x3 conv of layer k of BOTH towers on ALL levels is one grid (D._fwd_many / hd_conv2d_multi); GroupNorm + ReLU per tensor
         nl = len(feats)
@@ -80,7 +78,7 @@ class _HeadFn(torch.autograd.Function):
         outs = []
         for li in range(nl):
             outs += [h1[li], h1[nl + li], h2[li]]
-        ctx.head, ctx.saved, ctx.na, ctx.n = head, saved, n_active, feats[0].shape[0]
+        ctx.saved = saved
         return tuple(outs)
 
     @staticmethod
@@ -119,15 +117,9 @@ class _HeadFn(torch.autograd.Function):
                         D._bgrad_into(convs[k].bias, dc, inv)
                     d = _dgrad(tower[k][0], dc, (H, W), res=df if k == 0 else None)
                 df = d
-            if df is not None and na < ctx.n and not ctx.has_acts:
-                full = torch.zeros((ctx.n,) + tuple(df.shape[1:]), dtype=df.dtype, device=df.device)
-                full[:na] = df
-                df = full
             dfeats.append(df)
         ctx.saved = None
-        if ctx.has_acts:
-            return (None, None, None, None) + (None,) * len(dfeats) + tuple(dfeats)
-        return (None, None, None, None) + tuple(dfeats)
+        return D._head_exit(ctx, dfeats)
 
 
 class _GNTower(nn.Module):
@@ -171,34 +163,24 @@ class FCOSRegressionHead(_GNTower):
             nn.init.zeros_(l.bias)
 
 
-class FCOSHead(nn.Module):
+class FCOSHead(D._PyramidHead, nn.Module):
+    _Fn = _HeadFn
+
     def __init__(self, in_channels, num_anchors, num_classes):
         super().__init__()
         self.box_coder = BoxLinearCoder(normalize_by_size=True)
         self.classification_head = FCOSClassificationHead(in_channels, num_anchors, num_classes)
         self.regression_head = FCOSRegressionHead(in_channels, num_anchors)
-        self._pack, self._hook = None, None
-        self.train_params, self.grad_scale = False, 1.0
 
-    def invalidate(self):
-        self._pack = None
-
-    def pack(self):
-        if self._pack is None:
-            c, r = self.classification_head, self.regression_head
-            self._pack = dict(cls_tower=c.tower_entries(), cls_out=_conv_entry(c.cls_logits), reg_tower=r.tower_entries(),
-                              reg_out=_conv_entry(r.bbox_reg), ctr_out=_conv_entry(r.bbox_ctrness))
-        return self._pack
+    def _build_pack(self):
+        c, r = self.classification_head, self.regression_head
+        return dict(cls_tower=c.tower_entries(), cls_out=_conv_entry(c.cls_logits), reg_tower=r.tower_entries(),
+                    reg_out=_conv_entry(r.bbox_reg), ctr_out=_conv_entry(r.bbox_ctrness))
 
     def forward(self, x, n_active=None):
         """x: list of NHWC fp16 feature maps -> {'cls_logits' [N, sum(HW*A), K], 'bbox_regression' [N, sum(HW*A), 4] (>= 0),
         'bbox_ctrness' [N, sum(HW*A), 1]} fp32."""
-        feats = list(x)
-        if self._hook is None or self._hook.device != feats[0].device:
-            self._hook = torch.zeros(1, device=feats[0].device, requires_grad=True)
-        na = feats[0].shape[0] if n_active is None else n_active
-        acts = D._active_views(feats, na) if na < feats[0].shape[0] else None
-        outs = _HeadFn.apply(self._hook, self, na, len(feats), *feats, *(acts or ()))
+        outs = self._run(x, n_active)
         K = self.classification_head.cls_logits.out_channels // self.classification_head.num_anchors
 
         def flat(t, k):
@@ -220,62 +202,15 @@ def _default_anchorgen():
     return D.AnchorGenerator(((8,), (16,), (32,), (64,), (128,)), ((1.0,),) * 5)
 
 
-class FCOS(nn.Module):
+class FCOS(OneStageDetector):
+    """Trainable under `set_trainable` (train_detector.py with detector_name='fcos'): body.layer2-4, FPN incl. P6/P7, both head towers
+    with their GroupNorm affines and the three output convs."""
+
     def __init__(self, num_classes=91, min_size=800, max_size=1333, center_sampling_radius=1.5, score_thresh=0.2, nms_thresh=0.6,
                  detections_per_img=100, topk_candidates=1000):
-        super().__init__()
-        self.backbone = D.BackboneWithFPN(returned_layers=(2, 3, 4), extra_blocks=D.LastLevelP6P7(256, 256))
-        self.anchor_generator = _default_anchorgen()
-        self.head = FCOSHead(256, self.anchor_generator.num_anchors_per_location()[0], num_classes)
+        super().__init__(_default_anchorgen(), FCOSHead, num_classes, score_thresh, nms_thresh, detections_per_img, topk_candidates)
         self.box_coder = BoxLinearCoder(normalize_by_size=True)
-        # torchvision's GeneralizedRCNNTransform is always replaced by the reference (detector.py:43-48); build that one.
-        self.transform = D.CustomGeneralizedRCNNTransform(min_size=300, max_size=300, image_mean=[0.0], image_std=[1.0],
-                                                          size_divisible=1, fixed_size=(300, 300))
         self.center_sampling_radius = center_sampling_radius
-        self.score_thresh, self.nms_thresh = score_thresh, nms_thresh
-        self.detections_per_img, self.topk_candidates = detections_per_img, topk_candidates
-        self.batched_heads = True
-
-    def invalidate_packs(self):
-        self.backbone.invalidate()
-        self.head.invalidate()
-
-    def set_trainable(self, flag=True, grad_scale=1.0):
-        """Detector fine-tuning switch (train_detector.py with detector_name='fcos'): parameter gradients for what torchvision's
-        fcos_resnet50_fpn leaves trainable (trainable_backbone_layers=3 [EXT]: body.layer2-4, FPN incl. P6/P7, both head towers
-        with their GroupNorm affines and the three output convs)."""
-        for m in (self.backbone, self.head):
-            m.train_params, m.grad_scale = bool(flag), float(grad_scale)
-        for name, p in self.backbone.body.named_parameters():
-            p.requires_grad_(bool(flag) and name.split(".")[0] in ("layer2", "layer3", "layer4"))
-        for mod in (self.backbone.fpn, self.head):
-            for p in mod.parameters():
-                p.requires_grad_(bool(flag))
-
-    def trainable_parameters(self):
-        return [p for p in self.parameters() if p.requires_grad]
-
-    @staticmethod
-    def remap_state_dict_keys(state_dict):
-        """torchvision >= 0.13 key names -> the 0.12 names this module uses (FPN convs wrapped in Conv2dNormActivation)."""
-        sd = OrderedDict()
-        for k, v in state_dict.items():
-            for i in range(3):
-                k = k.replace("fpn.inner_blocks.%d.0." % i, "fpn.inner_blocks.%d." % i).replace("fpn.layer_blocks.%d.0." % i, "fpn.layer_blocks.%d." % i)
-            if k.endswith("num_batches_tracked"):
-                continue
-            sd[k] = v
-        return sd
-
-    def load_state_dict(self, state_dict, strict=True):
-        out = super().load_state_dict(self.remap_state_dict_keys(state_dict), strict=strict)
-        self.invalidate_packs()
-        return out
-
-    def _apply(self, fn, *a, **k):
-        out = super()._apply(fn, *a, **k)
-        self.invalidate_packs()
-        return out
 
     # ------------------------------------------------------------------ target assignment + losses
     def match_batched(self, anchors0, gt, gvalid, num_anchors_per_level):
@@ -291,71 +226,26 @@ class FCOS(nn.Module):
                                              torch.cuda.current_stream().cuda_stream), "hd_fcos_match")
         return m
 
+    def loss_padded(self, anchors0, gt, glab, gvalid, head_outputs, napl):
+        return fcos_loss_batched(anchors0, gt, glab, head_outputs, self.match_batched(anchors0, gt, gvalid, napl))
+
     def compute_loss(self, targets, head_outputs, anchors, num_anchors_per_level):
         """torchvision FCOS.compute_loss signature (called by eval_forward_fcos.py:70)."""
-        dev = head_outputs["cls_logits"].device
-        gt, glab, gvalid = D.pad_targets(targets, dev)
-        m = self.match_batched(anchors[0], gt, gvalid, num_anchors_per_level)
-        return fcos_loss_batched(anchors[0], gt, glab, head_outputs, m)
+        gt, glab, gvalid = D.pad_targets(targets, head_outputs["cls_logits"].device)
+        return self.loss_padded(anchors[0], gt, glab, gvalid, head_outputs, num_anchors_per_level)
 
-    # ------------------------------------------------------------------ reference-shaped (list based) post-processing
-    def postprocess_detections(self, head_outputs, anchors, image_shapes):
-        """torchvision FCOS.postprocess_detections [EXT]: per image, per level: score = sqrt(sigmoid(cls) * sigmoid(ctr)) >
-        score_thresh, top-k (1000) candidates, decode + clip; then class-aware NMS (0.6) and the first detections_per_img."""
-        class_logits, box_regression, box_ctrness = head_outputs["cls_logits"], head_outputs["bbox_regression"], head_outputs["bbox_ctrness"]
-        detections = []
-        for index in range(len(image_shapes)):
-            ib, is_, il = [], [], []
-            for breg, logits, ctr, anc in zip((b[index] for b in box_regression), (c[index] for c in class_logits),
-                                              (c[index] for c in box_ctrness), anchors[index]):
-                num_classes = logits.shape[-1]
-                scores = torch.sqrt(torch.sigmoid(logits.detach()) * torch.sigmoid(ctr.detach())).flatten()
-                keep = scores > self.score_thresh
-                scores, topk_idxs = scores[keep], torch.where(keep)[0]
-                num_topk = min(self.topk_candidates, topk_idxs.size(0))
-                order = torch.sort(scores, descending=True, stable=True)[1][:num_topk]
-                scores, topk_idxs = scores[order], topk_idxs[order]
-                anchor_idxs = torch.div(topk_idxs, num_classes, rounding_mode="floor")
-                boxes = self.box_coder.decode_single(breg.detach()[anchor_idxs], anc[anchor_idxs])
-                ib.append(D.clip_boxes_to_image(boxes, image_shapes[index]))
-                is_.append(scores)
-                il.append(topk_idxs % num_classes)
-            ib, is_, il = torch.cat(ib, 0), torch.cat(is_, 0), torch.cat(il, 0)
-            order, sel, _ = D._batched_nms_padded(ib[None], is_[None], il[None], torch.ones_like(is_[None], dtype=torch.bool),
-                                                  self.nms_thresh, self.detections_per_img)
-            keep = order[0][sel[0]]
-            detections.append({"boxes": ib[keep], "scores": is_[keep], "labels": il[keep]})
-        return detections
+    def _scores(self, outputs):
+        return torch.sqrt(torch.sigmoid(outputs["cls_logits"].detach()) * torch.sigmoid(outputs["bbox_ctrness"].detach()))
 
-    # ------------------------------------------------------------------ batched form (no per-image / per-level host syncs)
-    def postprocess_detections_padded(self, head_outputs, anchors0, napl, image_shape):
-        """Same selection on padded tensors.  Returns boxes [B, D, 4], scores [B, D], labels [B, D], counts [B]."""
-        cls_logits, bbox_regression, ctr = head_outputs["cls_logits"], head_outputs["bbox_regression"], head_outputs["bbox_ctrness"]
-        B, A, K = cls_logits.shape
-        # all levels at once (as RetinaNet.postprocess_detections_padded): threshold, per-level top-k in one hd_topk_select_rows launch,
-        # one gather / decode / clip over the selected candidates
-        scores = torch.sqrt(torch.sigmoid(cls_logits.detach()) * torch.sigmoid(ctr.detach())).reshape(B, A * K)
-        key = torch.where(scores > self.score_thresh, scores, float("-inf"))
-        idx = ops.topk_rows_segments(key, [n * K for n in napl], self.topk_candidates)
-        sc = torch.gather(key, 1, idx)
-        valid = sc > float("-inf")
-        aidx = torch.div(idx, K, rounding_mode="floor")
-        breg = torch.gather(bbox_regression.detach(), 1, aidx[:, :, None].expand(-1, -1, 4))
-        boxes = self.box_coder.decode_single(breg.reshape(-1, 4), anchors0[aidx].reshape(-1, 4)).reshape(B, -1, 4)
-        cb = D.clip_boxes_to_image(boxes, image_shape)
-        cs = torch.where(valid, sc, 0.0)
-        cl = idx % K
-        pick, counts = D._batched_nms_pick(cb, cs, cl, valid, self.nms_thresh, self.detections_per_img)
-        return (torch.gather(cb, 1, pick[:, :, None].expand(-1, -1, 4)), torch.gather(cs, 1, pick), torch.gather(cl, 1, pick), counts)
+    def _decode_clip(self, breg, anchors, image_shape):
+        boxes = self.box_coder.decode_single(breg.reshape(-1, 4), anchors.reshape(-1, 4)).reshape(breg.shape)
+        return D.clip_boxes_to_image(boxes, image_shape)
 
 
 def fcos_resnet50_fpn(pretrained=False, progress=True, num_classes=91, pretrained_backbone=False, weights_path=None, **kwargs):
     """torchvision.models.detection.fcos_resnet50_fpn [EXT].  COCO weights cannot be downloaded offline: `pretrained=True` is
     accepted for signature compatibility and ignored unless `weights_path` points at a local torchvision state_dict."""
-    model = FCOS(num_classes=num_classes, **kwargs)
-    if weights_path is not None:
-        model.load_state_dict(torch.load(weights_path, map_location="cpu"))
-    return model
+    return D._load_local_weights(FCOS(num_classes=num_classes, **kwargs), weights_path)
 
 
 # ======================================================================================================================

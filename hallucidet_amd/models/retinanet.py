@@ -16,7 +16,6 @@ fp32 tensor ops on the GPU (IoU and NMS are HIP kernels); there is no CPU path.
 """
 import math
 import re
-from collections import OrderedDict
 
 import ctypes
 
@@ -28,6 +27,7 @@ from .. import ops
 from ..ops import ACT_RELU
 from . import detection as D
 from .detection import _conv_entry, _dgrad, _fwd
+from .one_stage import OneStageDetector
 
 
 class _HeadFn(torch.autograd.Function):
@@ -35,9 +35,7 @@ class _HeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, hook, head, n_active, nlev, *feats):
-        ctx.has_acts = len(feats) > nlev        # the [n_active] views the gradients are returned for (detection._active_views)
-        ctx.set_materialize_grads(False)          # unused outputs arrive as None in backward, not as zero-filled maps
-        feats = feats[:nlev]
+        feats = D._head_enter(ctx, head, n_active, nlev, feats)
         P = head.pack()
         # layer k of BOTH towers on ALL levels is one grid (2 x levels independent 3x3 convs; D._fwd_many / hd_conv2d_multi): 5 launches
         # for the head instead of 50, the 10x10 / 5x5 levels riding in the tail of the 38x38 level's tiles
@@ -54,7 +52,7 @@ class _HeadFn(torch.autograd.Function):
         for li in range(nl):
             outs.append(heads[li])
             outs.append(heads[nl + li])
-        ctx.head, ctx.saved, ctx.na, ctx.n = head, saved, n_active, feats[0].shape[0]
+        ctx.saved = saved
         ctx.feats = [f[:n_active] for f in feats] if head.train_params else None
         return tuple(outs)
 
@@ -80,9 +78,7 @@ class _HeadFn(torch.autograd.Function):
             df = D._dgrad_many([P["cls_tower"][0]] * nl, d[:nl], hws)
             dfeats = D._dgrad_many([P["reg_tower"][0]] * nl, d[nl:], hws, ress=df)
             ctx.saved = None
-            if ctx.has_acts:
-                return (None, None, None, None) + (None,) * len(dfeats) + tuple(dfeats)
-            return (None, None, None, None) + tuple(dfeats)
+            return D._head_exit(ctx, dfeats)
         for i, lv in enumerate(ctx.saved):
             df = None
             for j, (tower, last) in enumerate(((P["cls_tower"], P["cls_out"]), (P["reg_tower"], P["reg_out"]))):
@@ -106,15 +102,9 @@ class _HeadFn(torch.autograd.Function):
                     D._wgrad_into(convs[0].weight, tower[0], ctx.feats[i], d, inv)
                     D._bgrad_into(convs[0].bias, d, inv)
                 df = _dgrad(tower[0], d, (H, W), res=df)
-            if df is not None and na < ctx.n and not ctx.has_acts:
-                full = torch.zeros((ctx.n,) + tuple(df.shape[1:]), dtype=df.dtype, device=df.device)
-                full[:na] = df
-                df = full
             dfeats.append(df)
         ctx.saved = None
-        if ctx.has_acts:
-            return (None, None, None, None) + (None,) * len(dfeats) + tuple(dfeats)
-        return (None, None, None, None) + tuple(dfeats)
+        return D._head_exit(ctx, dfeats)
 
 
 class _Tower(nn.Module):
@@ -152,32 +142,21 @@ class RetinaNetRegressionHead(_Tower):
         nn.init.zeros_(self.bbox_reg.bias)
 
 
-class RetinaNetHead(nn.Module):
+class RetinaNetHead(D._PyramidHead, nn.Module):
+    _Fn = _HeadFn
+
     def __init__(self, in_channels, num_anchors, num_classes):
         super().__init__()
         self.classification_head = RetinaNetClassificationHead(in_channels, num_anchors, num_classes)
         self.regression_head = RetinaNetRegressionHead(in_channels, num_anchors)
-        self._pack, self._hook = None, None
-        self.train_params, self.grad_scale = False, 1.0
 
-    def invalidate(self):
-        self._pack = None
-
-    def pack(self):
-        if self._pack is None:
-            c, r = self.classification_head, self.regression_head
-            self._pack = dict(cls_tower=c.tower_entries(), cls_out=_conv_entry(c.cls_logits),
-                              reg_tower=r.tower_entries(), reg_out=_conv_entry(r.bbox_reg))
-        return self._pack
+    def _build_pack(self):
+        c, r = self.classification_head, self.regression_head
+        return dict(cls_tower=c.tower_entries(), cls_out=_conv_entry(c.cls_logits), reg_tower=r.tower_entries(), reg_out=_conv_entry(r.bbox_reg))
 
     def forward(self, x, n_active=None):
         """x: list of NHWC fp16 feature maps -> {'cls_logits': [N, sum(H*W*A), K], 'bbox_regression': [N, sum(H*W*A), 4]} fp32."""
-        feats = list(x)
-        if self._hook is None or self._hook.device != feats[0].device:
-            self._hook = torch.zeros(1, device=feats[0].device, requires_grad=True)
-        na = feats[0].shape[0] if n_active is None else n_active
-        acts = D._active_views(feats, na) if na < feats[0].shape[0] else None
-        outs = _HeadFn.apply(self._hook, self, na, len(feats), *feats, *(acts or ()))
+        outs = self._run(x, n_active)
         K = self.classification_head.cls_logits.out_channels // self.classification_head.num_anchors
         cls, reg = [], []
         for c, r in zip(outs[0::2], outs[1::2]):
@@ -192,127 +171,35 @@ def _default_anchorgen():
     return D.AnchorGenerator(sizes, ((0.5, 1.0, 2.0),) * len(sizes))
 
 
-class RetinaNet(nn.Module):
+class RetinaNet(OneStageDetector):
+    """Trainable under `set_trainable` (train_detector.py with detector_name='retinanet'): body.layer2-4, FPN incl. P6/P7, both head
+    towers and their output convs."""
+    # torchvision >= 0.13 also wraps the tower convs: head.<h>.conv.<i>.0.weight -> head.<h>.conv.<2i>.weight
+    _rewrite_key = staticmethod(lambda k: re.sub(r"(head\.\w+_head\.conv\.)(\d)\.0\.", lambda m: "%s%d." % (m.group(1), 2 * int(m.group(2))), k))
+
     def __init__(self, num_classes=91, min_size=800, max_size=1333, score_thresh=0.05, nms_thresh=0.5, detections_per_img=300,
                  fg_iou_thresh=0.5, bg_iou_thresh=0.4, topk_candidates=1000):
-        super().__init__()
-        self.backbone = D.BackboneWithFPN(returned_layers=(2, 3, 4), extra_blocks=D.LastLevelP6P7(256, 256))
-        self.anchor_generator = _default_anchorgen()
-        self.head = RetinaNetHead(256, self.anchor_generator.num_anchors_per_location()[0], num_classes)
+        super().__init__(_default_anchorgen(), RetinaNetHead, num_classes, score_thresh, nms_thresh, detections_per_img, topk_candidates)
         self.proposal_matcher = D.Matcher(fg_iou_thresh, bg_iou_thresh, allow_low_quality_matches=True)
         self.box_coder = D.BoxCoder((1.0, 1.0, 1.0, 1.0))
-        # torchvision's GeneralizedRCNNTransform is always replaced by the reference (detector.py:43-48); build that one.
-        self.transform = D.CustomGeneralizedRCNNTransform(min_size=300, max_size=300, image_mean=[0.0], image_std=[1.0],
-                                                          size_divisible=1, fixed_size=(300, 300))
-        self.score_thresh, self.nms_thresh = score_thresh, nms_thresh
-        self.detections_per_img, self.topk_candidates = detections_per_img, topk_candidates
-        self.batched_heads = True
 
-    def invalidate_packs(self):
-        self.backbone.invalidate()
-        self.head.invalidate()
+    def _scores(self, outputs):
+        return torch.sigmoid(outputs["cls_logits"].detach())
 
-    def set_trainable(self, flag=True, grad_scale=1.0):
-        """Detector fine-tuning switch (train_detector.py with detector_name='retinanet'): parameter gradients for what
-        torchvision's retinanet_resnet50_fpn leaves trainable (trainable_backbone_layers=3 [EXT]: body.layer2-4, FPN incl.
-        P6/P7, both head towers and their output convs)."""
-        for m in (self.backbone, self.head):
-            m.train_params, m.grad_scale = bool(flag), float(grad_scale)
-        for name, p in self.backbone.body.named_parameters():
-            p.requires_grad_(bool(flag) and name.split(".")[0] in ("layer2", "layer3", "layer4"))
-        for mod in (self.backbone.fpn, self.head):
-            for p in mod.parameters():
-                p.requires_grad_(bool(flag))
-
-    def trainable_parameters(self):
-        return [p for p in self.parameters() if p.requires_grad]
-
-    @staticmethod
-    def remap_state_dict_keys(state_dict):
-        """torchvision >= 0.13 key names -> the 0.12 names this module (and the reference's checkpoints) use."""
-        sd = OrderedDict()
-        for k, v in state_dict.items():
-            for i in range(3):                       # torchvision >= 0.13 wraps the FPN convs in Conv2dNormActivation
-                k = k.replace("fpn.inner_blocks.%d.0." % i, "fpn.inner_blocks.%d." % i).replace("fpn.layer_blocks.%d.0." % i, "fpn.layer_blocks.%d." % i)
-            # ... and the tower convs: head.<h>.conv.<i>.0.weight -> head.<h>.conv.<2i>.weight
-            k = re.sub(r"(head\.\w+_head\.conv\.)(\d)\.0\.", lambda m: "%s%d." % (m.group(1), 2 * int(m.group(2))), k)
-            if k.endswith("num_batches_tracked"):
-                continue
-            sd[k] = v
-        return sd
-
-    def load_state_dict(self, state_dict, strict=True):
-        sd = self.remap_state_dict_keys(state_dict)
-        out = super().load_state_dict(sd, strict=strict)
-        self.invalidate_packs()
-        return out
-
-    def _apply(self, fn, *a, **k):
-        out = super()._apply(fn, *a, **k)
-        self.invalidate_packs()
-        return out
-
-    # ------------------------------------------------------------------ reference-shaped (list based) post-processing
-    def postprocess_detections(self, head_outputs, anchors, image_shapes):
-        """torchvision 0.12 RetinaNet.postprocess_detections [EXT]: per image, per level: sigmoid, > score_thresh, top-k
-        (1000) candidates, decode + clip; then class-aware NMS (0.5) and the first detections_per_img."""
-        class_logits, box_regression = head_outputs["cls_logits"], head_outputs["bbox_regression"]
-        detections = []
-        for index in range(len(image_shapes)):
-            ib, is_, il = [], [], []
-            for breg, logits, anc in zip((b[index] for b in box_regression), (c[index] for c in class_logits), anchors[index]):
-                num_classes = logits.shape[-1]
-                scores = torch.sigmoid(logits.detach()).flatten()
-                keep = scores > self.score_thresh
-                scores, topk_idxs = scores[keep], torch.where(keep)[0]
-                num_topk = min(self.topk_candidates, topk_idxs.size(0))
-                order = torch.sort(scores, descending=True, stable=True)[1][:num_topk]
-                scores, topk_idxs = scores[order], topk_idxs[order]
-                anchor_idxs = torch.div(topk_idxs, num_classes, rounding_mode="floor")
-                boxes = self.box_coder.decode_single(breg.detach()[anchor_idxs], anc[anchor_idxs])
-                ib.append(D.clip_boxes_to_image(boxes, image_shapes[index]))
-                is_.append(scores)
-                il.append(topk_idxs % num_classes)
-            ib, is_, il = torch.cat(ib, 0), torch.cat(is_, 0), torch.cat(il, 0)
-            order, sel, _ = D._batched_nms_padded(ib[None], is_[None], il[None], torch.ones_like(is_[None], dtype=torch.bool),
-                                                  self.nms_thresh, self.detections_per_img)
-            keep = order[0][sel[0]]
-            detections.append({"boxes": ib[keep], "scores": is_[keep], "labels": il[keep]})
-        return detections
-
-    # ------------------------------------------------------------------ batched form (no per-image / per-level host syncs)
-    def postprocess_detections_padded(self, cls_logits, bbox_regression, anchors0, napl, image_shape):
-        """Same selection on padded tensors.  cls_logits [B, A, K], bbox_regression [B, A, 4], anchors0 [A, 4], napl =
-        anchors per level.  Returns boxes [B, D, 4], scores [B, D], labels [B, D], counts [B] (D = detections_per_img)."""
-        B, A, K = cls_logits.shape
-        # every level's score > thresh / top-k (1000) in ONE launch: hd_topk_select_rows over the level segments of the [B, A*K] score
-        # rows returns, per segment, the row indices of its largest entries in descending order, ties by ascending index -- what the
-        # per-level `sort(descending, stable)[:k]` of the list form gives; candidates at or below the threshold carry -inf.
-        scores = torch.sigmoid(cls_logits.detach().reshape(B, A * K))
-        key = torch.where(scores > self.score_thresh, scores, float("-inf"))
-        idx = ops.topk_rows_segments(key, [n * K for n in napl], self.topk_candidates)          # [B, sum(min(k, n*K))]
-        sc = torch.gather(key, 1, idx)
-        valid = sc > float("-inf")
-        aidx = torch.div(idx, K, rounding_mode="floor")                                           # anchor index within the image
-        breg = torch.gather(bbox_regression.detach(), 1, aidx[:, :, None].expand(-1, -1, 4))
-        anc = anchors0[aidx]
+    def _decode_clip(self, breg, anchors, image_shape):
         # BoxCoder.decode_single + clip_boxes_to_image of the selected candidates in one launch (was ~25 elementwise launches per level)
-        cb = ops.roi_decode_clip(breg.reshape(-1, 4), anc.reshape(-1, 4), self.box_coder.weights, self.box_coder.bbox_xform_clip,
-                                 image_shape).reshape(B, -1, 4)
-        cs = torch.where(valid, sc, 0.0)
-        cl = idx % K
-        pick, counts = D._batched_nms_pick(cb, cs, cl, valid, self.nms_thresh, self.detections_per_img)
-        return (torch.gather(cb, 1, pick[:, :, None].expand(-1, -1, 4)), torch.gather(cs, 1, pick), torch.gather(cl, 1, pick), counts)
+        return ops.roi_decode_clip(breg.reshape(-1, 4), anchors.reshape(-1, 4), self.box_coder.weights, self.box_coder.bbox_xform_clip,
+                                   image_shape).reshape(breg.shape)
+
+    def loss_padded(self, anchors0, gt, glab, gvalid, head_outputs, napl=None):
+        return retinanet_loss_batched(self, anchors0, gt, glab, gvalid, head_outputs["cls_logits"], head_outputs["bbox_regression"])
 
 
 def retinanet_resnet50_fpn(pretrained=False, progress=True, num_classes=91, pretrained_backbone=False, weights_path=None, **kwargs):
     """torchvision.models.detection.retinanet_resnet50_fpn [EXT].  COCO weights cannot be downloaded offline:
     `pretrained=True` is accepted for signature compatibility and ignored unless `weights_path` points at a local
     torchvision state_dict (same policy as fasterrcnn_resnet50_fpn)."""
-    model = RetinaNet(num_classes=num_classes, **kwargs)
-    if weights_path is not None:
-        model.load_state_dict(torch.load(weights_path, map_location="cpu"))
-    return model
+    return D._load_local_weights(RetinaNet(num_classes=num_classes, **kwargs), weights_path)
 
 
 # ======================================================================================================================

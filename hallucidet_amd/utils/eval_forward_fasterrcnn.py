@@ -288,23 +288,29 @@ def _target_dtypes(targets):
             raise TypeError(f"target labels must of int64 type, instead got {t['labels'].dtype}")
 
 
+def _set_mode(model, train_det):
+    """The first lines of every eval_forward_*: the frozen detector runs in eval mode; with `train_det` (train_detector.py:159) the
+    module's mode is left as the caller set it (Lightning: train()), and parameter gradients need `set_trainable(True)` (DetectorLit
+    does it), otherwise nothing would be learned."""
+    if not train_det:
+        model.eval()
+    elif not getattr(model.backbone, "train_params", False):
+        raise RuntimeError("hallucidet_amd: train_det=True needs detector.set_trainable(True) first (see "
+                           "hallucidet_amd.train_detector.DetectorLit); the frozen-detector kernels emit data gradients only")
+
+
+def _hw_of(img):
+    hw = img.shape[-2:]
+    torch._assert(len(hw) == 2, f"expecting the last two dimensions of the Tensor to be H and W instead got {img.shape[-2:]}")
+    return (hw[0], hw[1])
+
+
 def eval_forward_fasterrcnn(model, images, targets, train_det=False, model_name='fasterrcnn'):
     """One detector pass that returns the training losses AND the detections (reference :13-68; the error texts are the reference's).
     `model.batched_heads` (default) runs the two stages in padded, batched form (`_heads_batched`); otherwise the list forms below."""
-    if train_det:
-        # train_detector.py:159 -- the module's mode is left as the caller set it (Lightning: train()); parameter
-        # gradients need FasterRCNN.set_trainable(True) (DetectorLit does it), otherwise nothing would be learned
-        if not getattr(model.backbone, "train_params", False):
-            raise RuntimeError("hallucidet_amd: train_det=True needs detector.set_trainable(True) first (see "
-                               "hallucidet_amd.train_detector.DetectorLit); the frozen-detector kernels emit data gradients only")
-    else:
-        model.eval()
+    _set_mode(model, train_det)
     _check_targets(targets)
-    sizes_in = []
-    for img in images:
-        hw = img.shape[-2:]
-        torch._assert(len(hw) == 2, f"expecting the last two dimensions of the Tensor to be H and W instead got {img.shape[-2:]}")
-        sizes_in.append((hw[0], hw[1]))
+    sizes_in = [_hw_of(img) for img in images]
     images, targets = model.transform(images, targets)
     if targets is not None:
         _check_degenerate(targets)               # (:41-53) one fused test, the reference's message

@@ -4,14 +4,15 @@ box_loss :53-80, eval_forward_retinanet :83-160, compute_retinanet_loss :163-178
 ({'classification', 'bbox_regression'}) and the same call sequence on the model (transform -> backbone -> head ->
 anchor_generator -> losses -> postprocess_detections -> transform.postprocess).
 
-The per-image python loops of the loss and the per-image / per-level loops of the post-processing run in padded,
-batched form when `model.batched_heads` is set (hallucidet_amd.models.retinanet; same arithmetic -- the GPU tests assert
-equality with the list-based functions below, which stay for exactly that purpose and for API compatibility)."""
+The pass itself is eval_forward_one_stage.py's (shared with FCOS).  The per-image python loops of the loss and the per-image /
+per-level loops of the post-processing run in padded, batched form when `model.batched_heads` is set (same arithmetic -- the GPU
+tests assert equality with the list-based functions below, which stay for exactly that purpose and for API compatibility)."""
 from typing import Dict, Optional
 
 import torch
 
-from .eval_forward_fasterrcnn import _check_degenerate, _check_targets, check_degenerate_deferred
+from .eval_forward_fasterrcnn import _hw_of      # noqa: F401  (the reference's helper; importable from here as before)
+from .eval_forward_one_stage import eval_forward_one_stage, eval_forward_one_stage_multi
 from ..models import detection as D
 from ..models import retinanet as R
 
@@ -77,92 +78,13 @@ def box_loss(type: str, box_coder, anchors_per_image: torch.Tensor, matched_gt_b
 
 
 def eval_forward_retinanet(model, images, targets, train_det=False, model_name='retinanet'):
-    if train_det:
-        if not getattr(model.backbone, "train_params", False):
-            raise RuntimeError("hallucidet_amd: train_det=True needs detector.set_trainable(True) first (see "
-                               "hallucidet_amd.train_detector.DetectorLit); the frozen-detector kernels emit data gradients only")
-    else:
-        model.eval()
-    _check_targets(targets)
-    original_image_sizes = [_hw_of(img) for img in images]
-
-    images, targets = model.transform(images, targets)
-    if targets is not None:
-        _check_degenerate(targets)
-
-    features = model.backbone(images.tensors)
-    features = [features] if isinstance(features, torch.Tensor) else list(features.values())
-    head_outputs, anchors = model.head(features), model.anchor_generator(images, features)
-    # anchors per level (the feature maps are NHWC here: H, W = size(1), size(2)); A = anchors per location
-    cells = [f.size(1) * f.size(2) for f in features]
-    per_cell = head_outputs["cls_logits"].size(1) // sum(cells)
-    napl = [c * per_cell for c in cells]
-
-    if getattr(model, "batched_heads", False):
-        gt, glab, gvalid = D.pad_targets(targets, images.tensors.device)
-        losses = R.retinanet_loss_batched(model, anchors[0], gt, glab, gvalid, head_outputs["cls_logits"], head_outputs["bbox_regression"])
-        return losses, _detections_padded(model, head_outputs, anchors[0], napl, images.image_sizes, original_image_sizes)
-
-    # list-based route (API compatibility with the reference's model methods; the GPU tests compare it with the batched one)
-    losses = compute_retinanet_loss(targets, head_outputs, anchors, model)
-    per_level_outputs = {k: list(v.split(napl, dim=1)) for k, v in head_outputs.items()}
-    per_level_anchors = [list(a.split(napl)) for a in anchors]
-    raw = model.postprocess_detections(per_level_outputs, per_level_anchors, images.image_sizes)
-    return losses, model.transform.postprocess(raw, images.image_sizes, original_image_sizes)
-
-
-def _hw_of(img):
-    hw = img.shape[-2:]
-    torch._assert(len(hw) == 2, f"expecting the last two dimensions of the Tensor to be H and W instead got {img.shape[-2:]}")
-    return (hw[0], hw[1])
-
-
-def _detections_padded(model, head_outputs, anchors0, napl, image_sizes, original_image_sizes):
-    """Deferred (LazyDetections.deferred): launched by the first access or by the training step's flush() after the backward pass."""
-    cls_logits, bbox_regression = head_outputs["cls_logits"].detach(), head_outputs["bbox_regression"].detach()
-    training = model.transform.training
-
-    def postprocess():
-        from ..models.custom_generalized_transform import _ratios
-        from .eval_forward_fasterrcnn import _scale_tensor
-        sb, ss, sl, counts = model.postprocess_detections_padded(cls_logits, bbox_regression, anchors0, napl, image_sizes[0])
-        scale = None
-        if not training:
-            rh, rw = _ratios(image_sizes[0], original_image_sizes[0])
-            scale = _scale_tensor(rw, rh, sb)
-        return sb, ss, sl, counts, ((lambda b: b * scale) if scale is not None else None)
-    return D.LazyDetections.deferred(postprocess, cls_logits.shape[0])
+    return eval_forward_one_stage(model, images, targets, train_det,
+                                  lambda targets, head_outputs, anchors, napl: compute_retinanet_loss(targets, head_outputs, anchors, model))
 
 
 def eval_forward_retinanet_multi(model, image_batches, target_lists, model_name='retinanet'):
-    """The hallucinated / RGB / IR detector passes of one training step (train_hallucidet.py:180,183,186) as ONE
-    transform + trunk + head evaluation over the concatenated batch (frozen eval-mode detector: images are independent).
-    Only the first batch carries a gradient and a loss (the reference discards the other two).  RetinaNet has no sampler,
-    so -- unlike the Faster R-CNN fusion -- the result is exactly that of three separate passes."""
-    model.eval()
-    for t in target_lists:
-        _check_targets(t)
-    sizes = [[(img.shape[-2], img.shape[-1]) for img in b] for b in image_batches]
-    nb = [len(s) for s in sizes]
-    flat_targets = [t for tl in target_lists for t in tl]
-    il, flat_targets = model.transform.forward_batches(image_batches, flat_targets)       # every batch resized into its slice: no fp32 concat
-    check_degenerate_deferred(model, flat_targets)          # no host synchronisation inside the step
-    n0 = nb[0]
-    if image_batches[0].requires_grad:
-        features = list(model.backbone(il.tensors, n_active=n0).values())
-        head_outputs = model.head(features, n_active=n0)
-    else:
-        with torch.no_grad():
-            features = list(model.backbone(il.tensors).values())
-            head_outputs = model.head(features)
-    anchors = model.anchor_generator(il, features)
-    napl = [f.size(1) * f.size(2) for f in features]
-    A = head_outputs["cls_logits"].size(1) // sum(napl)
-    napl = [n * A for n in napl]
-    gt, glab, gvalid = D.pad_targets(flat_targets[:n0], il.tensors.device)
-    losses = R.retinanet_loss_batched(model, anchors[0], gt, glab, gvalid, head_outputs["cls_logits"][:n0], head_outputs["bbox_regression"][:n0])
-    dets = _detections_padded(model, head_outputs, anchors[0], napl, il.image_sizes, sizes[0]).split(nb)
-    return [(losses if k == 0 else {}, d) for k, d in enumerate(dets)]
+    """The three detector passes of one training step as one evaluation (eval_forward_one_stage_multi)."""
+    return eval_forward_one_stage_multi(model, image_batches, target_lists)
 
 
 def _matched_padded(targets, anchors, model):

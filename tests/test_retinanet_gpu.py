@@ -135,7 +135,7 @@ def test_postprocess_exact_on_same_head_outputs(dev, case):
     got = det.postprocess_detections(split, [list(a.split(napl)) for a in anchors], il.image_sizes)
     osplit = {k: [t.cpu() for t in v] for k, v in split.items()}
     want = oracle.postprocess_detections(osplit, [list(a.cpu().split(napl)) for a in anchors], [(300, 300)] * 3)
-    sb, ss, sl, counts = det.postprocess_detections_padded(ho["cls_logits"], ho["bbox_regression"], anchors[0], napl, (300, 300))
+    sb, ss, sl, counts = det.postprocess_detections_padded(ho, anchors[0], napl, (300, 300))
     n_nontrivial = 0
     for i, (g, w) in enumerate(zip(got, want)):
         assert torch.equal(g["labels"].cpu(), w["labels"]), i
