@@ -371,6 +371,8 @@ __device__ __forceinline__ void radix_find_digit(const int* hist, int remaining,
 // (key, index) pairs in LDS, a bitonic network orders them (k <= 4096).  Replaces torch.sort over [24, 16875] per level
 // (rocprim merge sort: ~45 launches per step for the RPN levels).
 __device__ __forceinline__ uint32_t order_key(float f) {
+  if (f != f) return 0xFFFFFFFFu;                           // every NaN, whatever its sign and payload: the one largest key (above +inf =
+                                                            // 0xFF800000) -- torch.sort lists the NaNs first, in index order
   uint32_t u = __float_as_uint(f == 0.f ? 0.f : f);        // -0.0 and +0.0 compare equal (ties go by index), as in torch.sort
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);        // larger float <=> larger key
 }
