@@ -68,6 +68,11 @@ class WgradArgs(C.Structure):
     ]
 
 
+class ThinDgradArgs(C.Structure):      # mirrors struct hd_thin_dgrad_args
+    _fields_ = [("ga", vp), ("gb", vp), ("wda", vp), ("wdb", vp), ("mask", vp), ("dx", vp), ("stride_a", c_i64), ("stride_b", c_i64)] + \
+               [(n, c_i32) for n in ("n", "hw", "C", "Ka", "Kb", "Ka_p", "Kb_p", "g_f16")]
+
+
 # name -> (restype, argtypes).  Must list every symbol include/hallucidet_hip.h declares
 # (tests/test_abi.py parses the header and checks this table and the .so against it).
 PROTOTYPES = {
@@ -84,6 +89,10 @@ PROTOTYPES = {
     "hd_conv_tune_w8": (C.c_int, [C.c_int, C.c_int]),
     "hd_conv_nominal_batch": (C.c_int, [C.c_int]),
     "hd_gemm_w8_mode": (C.c_int, [C.c_int]),
+    "hd_thin_gemm_mode": (C.c_int, [C.c_int]),
+    "hd_thin_gemm_on": (C.c_int, []),
+    "hd_thin_dgrad_pair": (C.c_int, [C.POINTER(ThinDgradArgs), vp]),
+    "hd_thin_dgrad_pair_multi": (C.c_int, [C.POINTER(ThinDgradArgs), C.c_int, vp]),
     "hd_wgrad_w8_blocks": (C.c_int, [C.POINTER(WgradArgs)]),
     "hd_wgrad_route": (C.c_int, [C.POINTER(WgradArgs), C.POINTER(c_i32)]),
     "hd_wgrad": (C.c_int, [C.POINTER(WgradArgs), vp]),

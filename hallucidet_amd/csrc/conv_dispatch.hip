@@ -141,6 +141,25 @@ static int choose_gemm8(const ConvP& p) {
   return 0;
 }
 
+// Thin-N forward problems (gemm_thin.hip: 1x1 / stride 1 onto <= 16 channels, fp32 output -- the RPN head's and the box predictor's
+// output layers) leave the igemm family's 32-wide tile for the LDS-free streaming kernel.  Bit-identical, so the rule is the eligibility
+// alone.  hd_thin_gemm_mode (tests / tools): -1 = this rule, 0 = never, 1 = on.  HD_THIN_GEMM=0: off (A/B).
+static int g_thin_mode = -1;
+static bool thin_on() {
+  static const int on = env_int("HD_THIN_GEMM", 1);
+  return on && g_thin_mode != 0;
+}
+extern "C" int hd_thin_gemm_mode(int mode) {
+  HD_CHECK_ARG(mode == -1 || mode == 0 || mode == 1, "hd_thin_gemm_mode: mode in {-1, 0, 1}");
+  g_thin_mode = mode;
+  return HD_OK;
+}
+extern "C" int hd_thin_gemm_on(void) { return thin_on() ? 1 : 0; }
+bool hd_thin_fwd_eligible(const ConvP& p);
+int hd_thin_fwd_rg(int64_t rows);
+void hd_thin_fwd_launch(const ConvP* ps, int n, hipStream_t s);
+static bool use_thin(const ConvP& p) { return thin_on() && g_small_ok && hd_thin_fwd_eligible(p); }
+
 // tuning hook (tools/tune_conv.py): force the tile / K-depth / stage choice of the igemm family; -1 = heuristic
 static int g_ov_bm = -1, g_ov_bn = -1, g_ov_bk = -1, g_ov_deep = -1;
 extern "C" int hd_conv_tune_override(int bm, int bn, int bk, int deep) {
@@ -249,13 +268,13 @@ static int choose_p8(const ConvP& p, bool allow_m160 = true) {
 }
 
 // The routing decision: made once per problem by route(); the entry points ask it, and the capability functions after it, instead of the use_* predicates.
-enum Family { F_SMALL, F_C64, F_STEM, F_C32, F_CAT, F_GEMM8, F_P8, F_M160, F_IGEMM };     // (the ids hd_conv2d_route reports)
+enum Family { F_SMALL, F_C64, F_STEM, F_C32, F_CAT, F_GEMM8, F_P8, F_M160, F_IGEMM, F_THIN = 10 };     // (the ids hd_conv2d_route reports; 9 = F_IGEMM with 64-deep K tiles)
 
 struct Route {
   Family fam;
   int bm, bn;          // F_IGEMM: the M x N tile
   bool use64, deep;    // F_IGEMM: 64-deep K tiles; the deep LDS ring
-  int cfg;             // F_P8: tile id 0..7 (hd_conv_launch_p8); F_GEMM8: 128 / 1128
+  int cfg;             // F_P8: tile id 0..7 (hd_conv_launch_p8); F_GEMM8: 128 / 1128; F_THIN: 32-row groups per wave
   int th, tw;          // F_M160: the pixel tile, (4, 40), (8, 40) or (4, 24)
   bool par;            // F_IGEMM: the four output-parity classes of a stride-2 data gradient, gridDim.y = 4
   int M;               // the rows the tile was chosen for: p.M, or the largest parity class (ph = pw = 0)
@@ -338,6 +357,7 @@ static Route route(const ConvP& p) {
   if (use_c32(p)) { r.fam = F_C32; return r; }
   if (use_cat(p)) { r.fam = F_CAT; return r; }
   if ((r.cfg = choose_gemm8(p))) { r.fam = F_GEMM8; return r; }
+  if (use_thin(p)) { r.fam = F_THIN; r.cfg = hd_thin_fwd_rg(p.M); return r; }
   // stride-2 data gradients: four output-parity classes, each walking only the taps that meet non-zero input (conv_params.h); tile choice
   // and grid are for the largest class.  in_dil == 2 makes every 8-wave tile ineligible (hd_conv_p8_eligible, hd_conv_m160_eligible) and
   // choose_tile sets use64 only where Cin % 64 == 0, i.e. cin8 % 8 == 0: the class form is never refused once `par` holds.
@@ -403,6 +423,7 @@ static int grid_blocks(const ConvP& p, const Route& r) {
     case F_C32: { const int t = p.N * hd_cdiv(p.Ho, 8) * hd_cdiv(p.Wo, 16); return t < 256 ? t : 256; }      // 8 x 16-pixel tiles, persistent blocks
     case F_CAT: return hd_conv_cat128to32_rows(p);
     case F_GEMM8: return hd_cdiv(p.M, r.cfg == 1128 ? 128 : 256) * hd_cdiv(p.Cout, 128);
+    case F_THIN: return hd_cdiv(p.M, 32 * r.cfg);                      // one-wave blocks
     case F_P8: return hd_conv_p8_tiles(p, r.cfg) * hd_cdiv(p.Cout, (r.cfg & 2) ? 64 : 128);
     case F_M160: return hd_conv_m160_tiles(p, r.th, r.tw) * hd_cdiv(p.Cout, 64);
     default: return hd_cdiv(r.M, r.bm) * hd_cdiv(p.Cout, r.bn) * (r.par ? 4 : 1);
@@ -412,7 +433,7 @@ static int grid_blocks(const ConvP& p, const Route& r) {
 // the single switch over the launchers; `wa`: the weight gradient that shares a F_P8 grid (carries_wgrad)
 static void launch(ConvP& p, const Route& r, hipStream_t s, const hd_wgrad_args* wa = nullptr) {
   static const int w8_prio = env_int("HD_W8_PRIO", 0);
-  if (r.fam >= F_P8) p.prio = w8_prio;
+  if (r.fam >= F_P8 && r.fam != F_THIN) p.prio = w8_prio;
   p.M = r.M, p.par = r.par;      // the launchers add gridDim.y = 4
   switch (r.fam) {
     case F_SMALL: hd_conv_launch_small(p, s); break;
@@ -423,6 +444,7 @@ static void launch(ConvP& p, const Route& r, hipStream_t s, const hd_wgrad_args*
     case F_GEMM8: hd_gemm_w8_launch(p, r.cfg, s); break;
     case F_P8: if (wa) hd_conv_launch_p8_wgrad(p, r.cfg, wa, s); else hd_conv_launch_p8(p, r.cfg, s); break;
     case F_M160: hd_conv_launch_m160(p, r.th, r.tw, s); break;
+    case F_THIN: hd_thin_fwd_launch(&p, 1, s); break;
     case F_IGEMM: if (r.use64) hd_conv_launch_bk64(p, r.bm, r.bn, r.deep, s); else hd_conv_launch_bk32(p, r.bm, r.bn, r.deep, s); break;
   }
 }
@@ -531,14 +553,14 @@ extern "C" int hd_conv2d_wgrad(const hd_conv_args* a, const hd_wgrad_args* wa, v
 // none of them claimed by the small-channel or the 8-wave kernels).  The tile of the FIRST problem (callers put the largest first)
 // serves all of them: in this family the tile shape does not change a single output bit.  Otherwise the members the tile model sends
 // to the 96-pixel tile (conv3x3_m160.hip, cfg 10: the small pyramid levels) still share ONE grid -- the same blocks their own launches
-// would run, bit for bit -- and the others are launched one by one.  HD_CONV_MULTI=0: always separate launches, HD_CONV_M96_MULTI=0:
-// no 96-pixel grid (A/B).
+// would run, bit for bit -- and the others are launched one by one.  Thin-N members (route F_THIN) always form one grid of their own.
+// HD_CONV_MULTI=0: always separate launches, HD_CONV_M96_MULTI=0: no 96-pixel grid (A/B).
 extern "C" int hd_conv2d_multi(const hd_conv_args* args, int n, void* stream) {
   static const int multi_on = env_int("HD_CONV_MULTI", 1);
   static const int m96_multi_on = env_int("HD_CONV_M96_MULTI", 1);
   HD_CHECK_ARG(args && n >= 1, "hd_conv2d_multi: bad args");
   static ConvMulti mp;          // 3.3 KB: not on the stack of a ctypes call; the boundary is not re-entrant (SURVEY 8b "Threading")
-  bool taken[HD_CONV_MULTI_MAX] = {};
+  bool taken[HD_CONV_MULTI_MAX] = {}, thin[HD_CONV_MULTI_MAX] = {};
   int n96 = 0;                  // members of the 96-pixel grid (launched from two up)
   if (multi_on && n >= 2 && n <= HD_CONV_MULTI_MAX && g_small_ok && g_w8_cfg < 0) {
     Route rt[HD_CONV_MULTI_MAX];
@@ -548,6 +570,19 @@ extern "C" int hd_conv2d_multi(const hd_conv_args* args, int n, void* stream) {
       if (rc) return rc;
       rt[i] = route(mp.p[i]);
       igemm = igemm && shares_igemm_multi(mp.p[i], rt[i]) && rt[i].use64 == rt[0].use64;
+    }
+    // thin-N members (the 2 x levels output layers of a detection head, the predictor's two linears): ONE LDS-free grid, members that share
+    // their input paired (gemm_thin.hip); whatever else the group holds goes on below, one by one
+    int nthin = 0;
+    for (int i = 0; i < n; ++i) nthin += rt[i].fam == F_THIN;
+    if (nthin) {
+      static ConvP tp[HD_CONV_MULTI_MAX];
+      nthin = 0;
+      for (int i = 0; i < n; ++i)
+        if (rt[i].fam == F_THIN) { tp[nthin++] = mp.p[i]; thin[i] = true; }
+      hd_thin_fwd_launch(tp, nthin, (hipStream_t)stream);
+      HD_CHECK_LAUNCH();
+      igemm = false;
     }
     mp.n = n;
     if (igemm && (rt[0].use64 ? hd_conv_launch_bk64_multi(mp, rt[0].bm, rt[0].bn, rt[0].deep, (hipStream_t)stream)
@@ -570,7 +605,7 @@ extern "C" int hd_conv2d_multi(const hd_conv_args* args, int n, void* stream) {
     }
   }
   for (int i = 0; i < n; ++i) {
-    if (taken[i] && n96 >= 2) continue;
+    if (thin[i] || (taken[i] && n96 >= 2)) continue;
     int rc = hd_conv2d(&args[i], stream);
     if (rc) return rc;
   }

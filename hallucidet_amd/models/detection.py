@@ -197,6 +197,16 @@ def _head_grads_nhwc16_many(gs, hws, cout_ps, dtype=None):
     return outs
 
 
+def _thin_pair_ok(ea, eb, gs):
+    """May the data gradients of the two 1x1 heads `ea`, `eb` over one tensor leave as one fused launch (ops.thin_dgrad_pair_many)?  fp16
+    storage, the thin-GEMM path in force, and every gradient in `gs` ([n, H, W, K] views) fp32 with dense images."""
+    if ea["wd"].dtype != torch.float16 or ea["k"] != 1 or eb["k"] != 1 or ea["cin_p"] % 32 or ea["cout_p"] > 16 or eb["cout_p"] > 16:
+        return False
+    if not ops.thin_gemm_on():
+        return False
+    return all(g.dtype == torch.float32 and g.numel() > 0 and g.stride()[1:] == (g.shape[2] * g.shape[3], g.shape[3], 1) for g in gs)
+
+
 def _dgrad(e, dy, in_hw, *, res=None, mask=None):
     return ops.conv2d(dy, e["wd"], e["k"], e["k"], stride=1, pad=e["k"] - 1 - e["pad"], in_dil=e["stride"], out_hw=in_hw,
                       cout=e["cin_p"], res=res, mask=mask)
@@ -798,6 +808,14 @@ class _RPNHeadFn(torch.autograd.Function):
             # frozen head, every level has both gradients (the training step): the three data-gradient convs of ALL levels as three
             # grids -- cls, then box (+ cls result as residual, ReLU mask), then the shared 3x3 conv -- instead of 3 x levels launches
             hws = [(t.shape[1], t.shape[2]) for t in ctx.ts]
+            pairs = [(grads[2 * i][:na].permute(0, 2, 3, 1), grads[2 * i + 1][:na].permute(0, 2, 3, 1)) for i in range(nl)]
+            if _thin_pair_ok(P["cls"], P["box"], [g for pr in pairs for g in pr]) and nl <= ops.THIN_MULTI_MAX:
+                # fp16 storage, dense fp32 gradients: the casts, both 1x1 data gradients, their sum and the ReLU mask of ALL levels in ONE
+                # LDS-free grid (hd_thin_dgrad_pair_multi), bit-identical to the three launches below
+                dts = ops.thin_dgrad_pair_many([(ga, gb, P["cls"]["wd"], P["box"]["wd"], t) for (ga, gb), t in zip(pairs, ctx.ts)])
+                dfeats = _dgrad_many([P["conv"]] * nl, dts, hws)
+                ctx.ts = None
+                return _head_exit(ctx, dfeats)
             both = _head_grads_nhwc16_many([grads[2 * i][:na] for i in range(nl)] + [grads[2 * i + 1][:na] for i in range(nl)], hws + hws,
                                            [P["cls"]["cout_p"]] * nl + [P["box"]["cout_p"]] * nl, P["cls"]["wf"].dtype)
             gls, grs = both[:nl], both[nl:]
@@ -1140,6 +1158,57 @@ class FastRCNNPredictor(_Packed, nn.Module):
         R = x.shape[0]
         cls, box = _fwd_many([P["cls"], P["box"]], [x, x], f32=True)          # the two tiny-N GEMMs (1024 -> K, 1024 -> 4K) as one grid
         return cls.view(R, -1), box.view(R, -1)
+
+
+class _BoxHeadPredictFn(torch.autograd.Function):
+    """TwoMLPHead -> FastRCNNPredictor as ONE node (both frozen, fp16 storage): the forward is the two modules' own, and with both output
+    gradients present the predictor's two pad-and-casts, its two data gradients and the ReLU mask of fc7's output leave as one fused launch
+    (ops.thin_dgrad_pair_many with the predictor's input h7 as the mask) -- the same bits as _PredictorFn.backward followed by the
+    hd_relu_bwd at the top of _MLPFn.backward (masking an f16 value commutes with the rounding that produced it)."""
+
+    @staticmethod
+    def forward(ctx, x, head, pred):
+        P, Q = head.pack(), pred.pack()
+        h6 = _fwd(P["fc6"], x, act=ACT_RELU)
+        h7 = _fwd(P["fc7"], h6, act=ACT_RELU)
+        R = x.shape[0]
+        cls, box = _fwd_many([Q["cls"], Q["box"]], [h7, h7], f32=True)
+        ctx.head, ctx.pred, ctx.h6, ctx.h7, ctx.xshape = head, pred, h6, h7, tuple(x.shape)
+        return cls.view(R, -1), box.view(R, -1)
+
+    @staticmethod
+    def backward(ctx, dc, db):
+        P, Q = ctx.head.pack(), ctx.pred.pack()
+        h6, h7 = ctx.h6, ctx.h7
+        R = h7.shape[0]
+        gs = [None if g is None else g.contiguous().view(R, 1, 1, -1) for g in (dc, db)]
+        if dc is not None and db is not None and _thin_pair_ok(Q["cls"], Q["box"], gs):
+            d7 = ops.thin_dgrad_pair_many([(gs[0], gs[1], Q["cls"]["wd"], Q["box"]["wd"], h7)])[0]
+        else:
+            d7 = None
+            if dc is not None:
+                g = ops.nchw_to_nhwc_resize(dc.contiguous().float().view(R, -1, 1, 1), 1, 1, Q["cls"]["cout_p"], dtype=Q["cls"]["wf"].dtype)
+                d7 = _dgrad(Q["cls"], g, (1, 1))
+            if db is not None:
+                g = ops.nchw_to_nhwc_resize(db.contiguous().float().view(R, -1, 1, 1), 1, 1, Q["box"]["cout_p"], dtype=Q["box"]["wf"].dtype)
+                d7 = _dgrad(Q["box"], g, (1, 1), res=d7)
+            if d7 is None:
+                return None, None, None
+            d7 = ops.relu_bwd(d7.contiguous(), h7)
+        d6 = _dgrad(P["fc7"], d7, (1, 1), mask=h6)
+        dx = ops.conv2d(d6, P["fc6_t"], 1, 1, cout=P["fc6_t"].shape[0]).view(ctx.xshape)   # plain GEMM with the transposed fc6 matrix
+        ctx.h6 = ctx.h7 = None
+        return dx, None, None
+
+
+def box_head_predict(rh, pooled):
+    """rh.box_predictor(rh.box_head(pooled)).  With the stock head and predictor, both frozen, in fp16 storage, the gradient of `pooled`
+    wanted and the thin-GEMM path in force, the two run as one autograd node (_BoxHeadPredictFn); otherwise as the two calls."""
+    head, pred = rh.box_head, rh.box_predictor
+    if (type(head) is TwoMLPHead and type(pred) is FastRCNNPredictor and not head.train_params and not pred.train_params and pooled.shape[0] > 0
+            and pooled.dtype == torch.float16 and torch.is_grad_enabled() and pooled.requires_grad and ops.thin_gemm_on()):
+        return _BoxHeadPredictFn.apply(pooled, head, pred)
+    return pred(head(pooled))
 
 
 def fastrcnn_loss(class_logits, box_regression, labels, regression_targets):

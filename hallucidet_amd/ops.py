@@ -584,6 +584,51 @@ def pad_cast_f32_f16_many(xs, cps, dtype=None):
     return outs
 
 
+def thin_gemm_mode(mode):
+    """Test / A-B hook of the thin-GEMM kernels (hd_thin_gemm_mode): -1 rule, 0 never (the implicit-GEMM routes), 1 on."""
+    check(_abi.load().hd_thin_gemm_mode(int(mode)), "hd_thin_gemm_mode")
+
+
+def thin_gemm_on():
+    return _abi.load().hd_thin_gemm_on() == 1
+
+
+THIN_MULTI_MAX = 8      # HD_THIN_MULTI_MAX
+
+
+def thin_dgrad_pair_many(calls):
+    """calls: [(ga, gb, wda, wdb, mask)] -> [dx]: dx = f16(mask(f16(ga . wda) + gb . wdb)) per entry, all entries in ONE launch
+    (hd_thin_dgrad_pair_multi) -- the data gradients of two 1x1 heads over the same tensor, bit-identical to two pad-and-casts, the
+    first head's hd_conv2d and the second's with `res` / `mask`.  ga / gb: [n, H, W, K] fp32 with dense images (strides (*, W*K, K, 1): a
+    slice of a larger buffer), or f16 already padded to the weights' K; wda / wdb: f16 [C, K_p] (the w_dgrad layout); mask: f16 [n, H, W, C]
+    or None."""
+    assert 1 <= len(calls) <= THIN_MULTI_MAX
+    args, outs = [], []
+    for ga, gb, wda, wdb, mask in calls:
+        _need_cuda(ga, gb, wda, wdb, mask)
+        n, H, W, Ka = ga.shape
+        Kb = gb.shape[3]
+        C_, Kap = wda.shape
+        Kbp = wdb.shape[1]
+        assert gb.shape[:3] == ga.shape[:3] and wdb.shape[0] == C_ and wda.dtype == wdb.dtype == torch.float16 and wda.is_contiguous() and wdb.is_contiguous()
+        f16 = ga.dtype == torch.float16
+        assert gb.dtype == ga.dtype and ga.dtype in (torch.float16, torch.float32)
+        if f16:
+            assert ga.is_contiguous() and gb.is_contiguous() and Ka == Kap and Kb == Kbp
+            sa = sb = 0
+        else:
+            assert ga.stride()[1:] == (W * Ka, Ka, 1) and gb.stride()[1:] == (W * Kb, Kb, 1)
+            sa = max(ga.stride(0) if n > 1 else 0, H * W * Ka)
+            sb = max(gb.stride(0) if n > 1 else 0, H * W * Kb)
+        assert mask is None or (mask.shape == (n, H, W, C_) and mask.dtype == torch.float16 and mask.is_contiguous())
+        dx = torch.empty((n, H, W, C_), dtype=torch.float16, device=ga.device)
+        args.append(_abi.ThinDgradArgs(ptr(ga), ptr(gb), ptr(wda), ptr(wdb), ptr(mask), ptr(dx), sa, sb, n, H * W, C_, Ka, Kb, Kap, Kbp, 1 if f16 else 0))
+        outs.append(dx)
+    arr = (_abi.ThinDgradArgs * len(args))(*args)
+    check(_abi.load().hd_thin_dgrad_pair_multi(arr, len(args), _stream()), "hd_thin_dgrad_pair_multi")
+    return outs
+
+
 def maxpool3x3s2(x):
     N, H, W, C_ = x.shape
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1

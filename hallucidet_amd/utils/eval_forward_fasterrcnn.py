@@ -224,7 +224,7 @@ def _multi_fused(model, il, targets, nb, sizes, need_grad):
         S = rh.fg_bg_sampler.batch_size_per_image
         r0 = S * n0
         bf0 = D.roi_pool_rois(pool, features, rois[:r0], shape, n_images=n0)
-        cl0, br0 = pred(head(bf0))
+        cl0, br0 = D.box_head_predict(rh, bf0)          # one autograd node where both are frozen: the fused thin-K gradient pair
         with torch.no_grad():                          # the other passes' RoIs: forward only
             f_ng = OrderedDict((k, v.detach()) for k, v in features.items())
             cl1, br1 = pred(head(D.roi_pool_rois(pool, f_ng, rois[r0:], shape)))
@@ -246,7 +246,7 @@ def _multi_fused(model, il, targets, nb, sizes, need_grad):
     _raise_if_degenerate(flag, targets)            # read at the step's ONE host sync (the RoI sampler's counts, just above)
     r0 = sum(per[:n0])
     bf0 = D.roi_pool_rois(pool, features, rois[:r0], shape, n_images=n0)
-    cl0, br0 = pred(head(bf0))
+    cl0, br0 = D.box_head_predict(rh, bf0)
     with torch.no_grad():                          # the other passes' RoIs: forward only
         f_ng = OrderedDict((k, v.detach()) for k, v in features.items())
         cl1, br1 = pred(head(D.roi_pool_rois(pool, f_ng, rois[r0:], shape)))
@@ -343,7 +343,7 @@ def _heads_batched(model, images, features, objectness, deltas, targets):
     loss_objectness, loss_rpn_box_reg = D.rpn_targets_loss_batched(model.rpn, anchors[0], gt, gvalid, obj, dl)
     rh = model.roi_heads
     rois, labels, reg_t, per = D.select_training_samples_batched(rh, pb, pc, gt, glab, gvalid)
-    class_logits, box_regression = rh.box_predictor(rh.box_head(D.roi_pool_rois(rh.box_roi_pool, features, rois, shape)))
+    class_logits, box_regression = D.box_head_predict(rh, D.roi_pool_rois(rh.box_roi_pool, features, rois, shape))
     loss_classifier, loss_box_reg = D.fastrcnn_loss_flat(class_logits, box_regression, labels, reg_t)
     sb, ss, sl, counts = D.postprocess_detections_flat(rh, class_logits, box_regression, rois, per, shape)
     dets = [{"boxes": sb[i, :c], "labels": sl[i, :c], "scores": ss[i, :c]} for i, c in enumerate(counts.tolist())]
@@ -371,11 +371,12 @@ def rpn_eval(model, images, features, targets, head_out=None):
 def roi_heads_eval(model, features, proposals, image_shapes, targets=None, train_det=False):
     """List form of the RoI stage (reference :105-185): the training sampler also runs at evaluation time, the box head
     sees the SAMPLED proposals, and those are what is post-processed into detections."""
+    from ..models import detection as D
     rh = model.roi_heads
     if targets is not None:
         _target_dtypes(targets)
     proposals, _, labels, reg_targets = rh.select_training_samples(proposals, targets)
-    logits, regression = rh.box_predictor(rh.box_head(rh.box_roi_pool(features, proposals, image_shapes)))
+    logits, regression = D.box_head_predict(rh, rh.box_roi_pool(features, proposals, image_shapes))
     if labels is None:
         raise ValueError("labels cannot be None")
     if reg_targets is None:

@@ -126,7 +126,8 @@ int hd_conv2d_pool2_ok(const hd_conv_args* a);
 int hd_conv2d_stats_rows(const hd_conv_args* a);
 /* Read-only: which kernel hd_conv2d would launch for this argument block (the same routing decision, no launch, no HIP call).
  *   out[0] family: 0 small-channel 3x3, 1 64 -> 64, 2 stem, 3 32 -> 128, 4 cat 128 -> 32, 5 large-tile GEMM, 6 8-wave patch family,
- *          7 its 160- / 320- / 96-pixel tiles, 8 4-wave implicit GEMM with 32-deep K tiles, 9 the same with 64-deep K tiles
+ *          7 its 160- / 320- / 96-pixel tiles, 8 4-wave implicit GEMM with 32-deep K tiles, 9 the same with 64-deep K tiles,
+ *          10 the thin-N streaming kernel (gemm_thin.hip: 1x1 / stride 1 onto <= 16 channels, fp32 output; out[1] = 32-row groups per wave)
  *   out[1], out[2]: families 8 / 9: the M x N tile (bm, bn); 7: the pixel tile (th, tw); 6: the tile id 0..7, 0; 5: the tile (128 / 1128), 0;
  *          others 0, 0
  *   out[3] families 8 / 9: 1 = the deep (3-stage) ring; others 0
@@ -162,6 +163,33 @@ int hd_conv_nominal_batch(int n);
  * and fully connected layers -- on 256 x 128 (8 waves) / 128 x 128 (4 waves) tiles, register-only epilogue; bit-identical to the
  * implicit-GEMM family): -1 = the built-in rule, 0 = never, 128 / 1128 = that tile wherever the problem is eligible.  Process-wide. */
 int hd_gemm_w8_mode(int mode);
+/* test / A-B hook of the thin-GEMM path (gemm_thin.hip: LDS-free streaming kernels for the detector's thin 1x1 problems, bit-identical
+ * to the implicit-GEMM family): -1 = the built-in rule (on), 0 = never (hd_conv2d / hd_conv2d_multi keep the implicit-GEMM route), 1 = on.
+ * The environment variable HD_THIN_GEMM=0 switches the path off for the process whatever the mode.  Process-wide.
+ * hd_thin_gemm_on(): 1 if the path is in force (what a caller of hd_thin_dgrad_pair asks before it replaces its separate launches). */
+int hd_thin_gemm_mode(int mode);
+int hd_thin_gemm_on(void);
+
+/* Thin-K data-gradient pair: the data gradients of TWO 1x1 heads that read the same tensor (RPNHead.cls_logits + bbox_pred,
+ * FastRCNNPredictor.cls_score + bbox_pred [EXT]) summed, masked and rounded in one pass over the output,
+ *     dx[M][C] = f16( mask( f16(gA . WdA) + gB . WdB ) ),      M = n * hw rows,
+ * bit-identical to hd_pad_cast_f32_f16 of both gradients, hd_conv2d(gA) and hd_conv2d(gB, res = first result, mask) -- the first product
+ * is rounded to f16, converted back and added to the second fp32 accumulator, the mask (an element of `mask` > 0 keeps, anything else
+ * zeroes: a ReLU output) is applied, the sum is rounded once.  C % 32 == 0; Ka_p, Kb_p in {8, 16}; Ka <= Ka_p, Kb <= Kb_p. */
+typedef struct hd_thin_dgrad_args {
+  const void* ga;     /* g_f16 == 0: fp32 [n][hw][Ka], image i at ga + i * stride_a (a dense NHWC slice of a larger buffer);       */
+  const void* gb;     /* g_f16 == 1: f16 [M][Ka_p], already padded (padding channels zero).  gb likewise with Kb / Kb_p / stride_b */
+  const void* wda;    /* f16 [C][Ka_p]: the data-gradient layout of hd_weight_prep (w_dgrad) */
+  const void* wdb;    /* f16 [C][Kb_p] */
+  const void* mask;   /* f16 [M][C] or NULL */
+  void* dx;           /* f16 [M][C] */
+  int64_t stride_a, stride_b; /* elements between images of ga / gb (g_f16 == 0), >= hw * Ka / hw * Kb */
+  int32_t n, hw, C, Ka, Kb, Ka_p, Kb_p, g_f16;
+} hd_thin_dgrad_args;
+int hd_thin_dgrad_pair(const hd_thin_dgrad_args* a, void* stream);
+/* n <= 8 such problems (the pyramid levels) in ONE grid; no allocation, no host synchronisation (capturable). */
+#define HD_THIN_MULTI_MAX 8
+int hd_thin_dgrad_pair_multi(const hd_thin_dgrad_args* args, int n, void* stream);
 
 /* ------------------------------------------------------------------------
  * Weight-gradient implicit GEMM: dW[co][kh][kw][ci] = sum_pix dY[pix,co] * X[pix@(kh,kw),ci]
