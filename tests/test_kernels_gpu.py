@@ -2004,7 +2004,7 @@ def test_conv_stem_register_resident_kernel(dev, case):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("shape", [(2, 16, 20), (1, 13, 37), (8, 256, 320)])
+@pytest.mark.parametrize("shape", [(2, 16, 20), (1, 13, 37), (8, 256, 320), (2, 24, 4100)])      # the last: 1 542 tiles on 256 blocks at a small size
 def test_conv_32_to_128_register_resident_kernel(dev, shape):
     """conv3x3_c32to128.hip (decoder block 3's data gradient: 32 -> 128 channels) against the implicit-GEMM family (forced through the
     tuning override; same K order: outputs to an fp16 ulp) and ATen's fp32 convolution; runs bit-identical, image n == the image alone."""
@@ -2029,7 +2029,7 @@ def test_conv_32_to_128_register_resident_kernel(dev, shape):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("shape", [(2, 8, 10), (1, 7, 19), (8, 128, 160)])
+@pytest.mark.parametrize("shape", [(2, 8, 10), (1, 7, 19), (8, 128, 160), (2, 12, 2050)])       # the last: 1 542 tiles on 256 blocks at a small size
 def test_conv_upsample_concat_128_to_32_register_resident_kernel(dev, shape):
     """conv3x3_cat128to32.hip (decoder block 3's first convolution: cat([nearest_2x(a), skip]) 64 + 64 -> 32 channels, with BatchNorm
     partial sums) against the implicit-GEMM family (tuning override; outputs to an fp16 ulp, sums equal in their totals) and ATen's fp32
@@ -2058,6 +2058,65 @@ def test_conv_upsample_concat_128_to_32_register_resident_kernel(dev, shape):
     got2, stats2 = ops.conv2d(a, w, 3, 3, x2=skip, up1=True, pad=1, want_stats=True)
     assert torch.equal(got, got2) and torch.equal(stats, stats2)
     assert torch.equal(ops.conv2d(a[:1].contiguous(), w, 3, 3, x2=skip[:1].contiguous(), up1=True, pad=1)[0], got[0])
+
+
+WREG_EPILOGUE_CASES = [
+    # kernel, input (N, H, W)
+    ("c64", (1, 13, 37)),          # ragged in both directions, 6 tiles: fewer tiles than blocks
+    ("c64", (2, 24, 4100)),        # 1 542 tiles on 256 blocks: uneven multi-tile runs, the two-stage patch ring wraps
+    ("stem", (1, 27, 75)),         # output 14 x 38: ragged
+    ("stem", (1, 48, 8200)),       # output 24 x 4100: 1 542 tiles
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kernel,shape", WREG_EPILOGUE_CASES, ids=lambda v: v if isinstance(v, str) else "x".join(map(str, v)))
+def test_register_resident_epilogue_variants_equal_igemm(dev, kernel, shape):
+    """Every <STATS, EPI> instantiation of the two launch ladders over the shared scaffold (conv_wreg.h): conv3x3_c64.hip and
+    conv7x7s2_stem.hip with each combination of bias / residual / ReLU mask / ReLU, with and without BatchNorm partial sums, against
+    the implicit-GEMM family (forced through the tuning override; same K order and fp32 accumulation: outputs to an fp16 ulp, sums equal
+    in their totals), one partial row per persistent block, runs bit-identical.  The workload itself launches 4 of c64's 32 forward
+    variants and 2 of the stem's."""
+    import itertools
+    from hallucidet_amd import ops, _abi
+    N, H, W = shape
+    gen = torch.Generator().manual_seed(61)
+    if kernel == "c64":
+        x = rnd(N, H, W, 64, seed=62).to(dev)
+        w = rnd(64, 576, scale=1.0 / 24.0, seed=63).to(dev)
+        kw, forced, (Ho, Wo) = dict(pad=1), (128, 64, 64, 0), (H, W)
+    else:
+        x = torch.zeros(N, H, W, 8)
+        x[..., :3] = torch.rand(N, H, W, 3, generator=gen)
+        x = x.half().to(dev)
+        w4 = torch.zeros(64, 7, 7, 8)
+        w4[..., :3] = torch.randn(64, 7, 7, 3, generator=gen) * 0.08
+        w = w4.view(64, 392).half().to(dev)
+        kw, forced, (Ho, Wo) = dict(stride=2, pad=3), (128, 64, 32, 0), ((H - 1) // 2 + 1, (W - 1) // 2 + 1)
+    K = 3 if kernel == "c64" else 7
+    bias = (torch.randn(64, generator=gen) * 0.3).to(dev)
+    res = rnd(N, Ho, Wo, 64, seed=64).to(dev)
+    mask = (torch.rand(N, Ho, Wo, 64, generator=gen) > 0.4).half().to(dev)
+    tiles = N * ((Ho + 7) // 8) * ((Wo + 15) // 16)
+    lib = _abi.load()
+    for use_bias, use_res, use_mask, act, want_stats in itertools.product((False, True), (False, True), (False, True), (0, 1), (False, True)):
+        args = dict(kw, bias=bias if use_bias else None, res=res if use_res else None, mask=mask if use_mask else None, act=act, want_stats=want_stats)
+        tag = "bias=%d res=%d mask=%d act=%d stats=%d" % (use_bias, use_res, use_mask, act, want_stats)
+        got = ops.conv2d(x, w, K, K, **args)
+        lib.hd_conv_tune_override(*forced)
+        try:
+            ref = ops.conv2d(x, w, K, K, **args)
+        finally:
+            lib.hd_conv_tune_override(-1, -1, -1, -1)
+        got2 = ops.conv2d(x, w, K, K, **args)
+        if want_stats:
+            (got, stats), (ref, rstats), (got2, stats2) = got, ref, got2
+            assert stats.shape[0] == min(tiles, 256), tag                      # the persistent kernel really ran
+            assert torch.allclose(stats.sum(0), rstats.sum(0), rtol=2e-3, atol=2e-2), tag
+            assert torch.equal(stats, stats2), tag
+        assert got.shape == (N, Ho, Wo, 64), tag
+        assert float((got.float() - ref.float()).abs().max()) <= 2e-3 * max(1.0, float(ref.float().abs().max())), tag
+        assert torch.equal(got, got2), tag
 
 
 def _conv_args(x, w, y, *, x2=None, K=3, stride=1, pad=1, up1=False, stats=None):
