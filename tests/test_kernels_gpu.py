@@ -1831,6 +1831,96 @@ def test_roi_align_one_block_per_roi_and_channel_lane_gather_at_256_channels(dev
         assert float((err / (1e-2 + 2e-3 * want.abs())).max()) < 1.0, (l, float(err.max()))
 
 
+def test_roi_align_general_pooler_and_sampling_ratio_loops(dev):
+    """The loops every other RoIAlign test leaves out (they all pass 7, 7, 2): non-square and non-7x7 poolers, sampling ratios 1 and 3
+    and the adaptive grid (sampling_ratio 0, up to 4 x 1 samples per bin on the tall RoI and 105 x 63 on the one covering 40x the map)
+    -- the only code behind hd_roi_align_ml / hd_roi_align_ml_bwd for such a pooler and, since the single-level entries launch the
+    same kernels with a null level pointer, behind hd_roi_align / hd_roi_align_bwd.  Forward against the scalar oracle under fp16 and
+    fp32 storage; backward against the oracle's autograd (sampling ratios 1, 3; C = 64 adds the LDS-patch kernel) and, for the
+    adaptive grid, as the adjoint of the forward just pinned."""
+    from hallucidet_amd import ops
+    from oracle import detection as od
+    N, C = 2, 16
+    shapes = [(N, 13, 17, C), (N, 7, 9, C)]
+    scales = [1.0 / 8, 1.0 / 16]
+    feats = [rnd(*s, seed=150 + i) for i, s in enumerate(shapes)]
+    rois = torch.tensor([[0, 40.0, 40.0, 40.0, 40.0],          # the nine of test_roi_align_degenerate_and_outside_rois
+                         [1, 60.0, 30.0, 20.0, 10.0],
+                         [0, -400.0, -300.0, -200.0, -100.0],
+                         [1, 500.0, 400.0, 900.0, 700.0],
+                         [0, -8.0, -8.0, 0.0, 0.0],
+                         [1, 135.9, 103.9, 136.1, 104.1],
+                         [0, 33.3, 21.7, 33.9, 22.2],
+                         [1, -2000.0, -2000.0, 3000.0, 3000.0],
+                         [0, 0.0, 0.0, 135.99, 103.99],
+                         [0, 10.0, 8.0, 60.0, 90.0],           # five ordinary ones
+                         [1, 20.0, 4.0, 52.0, 92.0],           # tall: at 1/8 and 3 x 5 bins the adaptive grid is 4 x 1
+                         [0, 16.0, 8.0, 120.0, 100.0],
+                         [1, 5.5, 30.2, 77.7, 61.3],
+                         [1, 40.0, 0.0, 72.0, 110.0]])
+    levels = [0, 0, 0, 1, 0, 1, 0, 1, 0, 0, 0, 1, 1, 1]
+    outside = [2, 3]
+    R = rois.shape[0]
+    idx = [[i for i in range(R) if levels[i] == l] for l in range(2)]
+    lv_d, rois_d = torch.tensor(levels, dtype=torch.int32).to(dev), rois.to(dev)
+    bh, bw = (92.0 - 4.0) / 8 / 3, (52.0 - 20.0) / 8 / 5
+    assert math.ceil(bh) == 4 and math.ceil(bw) == 1
+    dout = rnd(R, 5, 5, C, seed=160)
+
+    def nhwc_grad(feat_shape, l, dy, P, sr):
+        f = torch.zeros(feat_shape[0], feat_shape[3], feat_shape[1], feat_shape[2], requires_grad=True)
+        od.roi_align_autograd(f, rois[idx[l]], P, scales[l], sr).backward(dy[idx[l]].float().permute(0, 3, 1, 2))
+        return ok.nchw_to_nhwc(f.grad)
+
+    for (PH, PW, sr) in ((3, 5, 0), (5, 5, 1), (5, 5, 3)):
+        want = [ok.roi_align_nchw(ok.nhwc_to_nchw(feats[l].float()), rois[idx[l]], PH, PW, scales[l], sr).permute(0, 2, 3, 1) for l in range(2)]
+        for dt in (torch.float16, torch.float32):
+            with ops.storage(dt):
+                fd = [f.to(dev, dt) for f in feats]
+                got = ops.roi_align_ml(fd, scales, rois_d, lv_d, PH, PW, sr).cpu()
+                single = [ops.roi_align(fd[l], rois_d[idx[l]].contiguous(), PH, PW, scales[l], sr).cpu() for l in range(2)]
+            for name, outs in (("multi-level", [got[idx[l]] for l in range(2)]), ("single-level", single)):
+                for l in range(2):
+                    o = outs[l]
+                    assert o.dtype == dt and o.shape == want[l].shape and torch.isfinite(o).all()
+                    if dt == torch.float16:
+                        close(o, want[l].half(), rtol=2e-3, atol=1e-3)
+                    else:
+                        assert torch.allclose(o, want[l], atol=2e-5), (name, PH, PW, sr, l, float((o - want[l]).abs().max()))
+                    for i in outside:
+                        if levels[i] == l:
+                            assert float(o[idx[l].index(i)].abs().max()) == 0.0          # entirely outside: exactly zero
+        if sr > 0:
+            dfs = ops.roi_align_ml_bwd(dout.to(dev), rois_d, lv_d, shapes, scales, sr)
+            for l in range(2):
+                wantg = nhwc_grad(shapes[l], l, dout, PH, sr)
+                single = ops.roi_align_bwd(dout[idx[l]].to(dev), rois_d[idx[l]].contiguous(), shapes[l], scales[l], sr)
+                for name, gotg in (("multi-level", dfs[l].cpu()), ("single-level", single.cpu())):
+                    assert torch.allclose(gotg, wantg, rtol=1e-3, atol=2e-3), (name, sr, l, float((gotg - wantg).abs().max()))
+        else:
+            dout35 = rnd(R, PH, PW, C, seed=161)
+            dfs = [d.cpu() for d in ops.roi_align_ml_bwd(dout35.to(dev), rois_d, lv_d, shapes, scales, sr)]
+            single = [ops.roi_align_bwd(dout35[idx[l]].to(dev), rois_d[idx[l]].contiguous(), shapes[l], scales[l], sr).cpu() for l in range(2)]
+            assert all(torch.isfinite(d).all() for d in dfs + single)
+            for seed in (170, 171, 172):
+                probe = [rnd(*s, seed=seed + 10 * l) for l, s in enumerate(shapes)]
+                out = ops.roi_align_ml([p.to(dev) for p in probe], scales, rois_d, lv_d, PH, PW, sr).float().cpu()
+                lhs = float((dout35.float() * out).sum())
+                rhs = sum(float((d * p.float()).sum()) for d, p in zip(dfs, probe))
+                assert abs(lhs - rhs) <= 2e-2 * max(1.0, abs(lhs)), ("multi-level", seed, lhs, rhs)
+                for l in range(2):
+                    lhs = float((dout35[idx[l]].float() * out[idx[l]]).sum())
+                    rhs = float((single[l] * probe[l].float()).sum())
+                    assert abs(lhs - rhs) <= 2e-2 * max(1.0, abs(lhs)), ("single-level", seed, l, lhs, rhs)
+    # C % 64 == 0: RoIs of at most 64 touched pixels go through the LDS-patch kernel, the rest through the direct atomics
+    shapes64 = [(N, 13, 17, 64), (N, 7, 9, 64)]
+    dout64 = rnd(R, 5, 5, 64, seed=162)
+    dfs = ops.roi_align_ml_bwd(dout64.to(dev), rois_d, lv_d, shapes64, scales, 3)
+    for l in range(2):
+        wantg = nhwc_grad(shapes64[l], l, dout64, 5, 3)
+        assert torch.allclose(dfs[l].cpu(), wantg, rtol=1e-3, atol=2e-3), (l, float((dfs[l].cpu() - wantg).abs().max()))
+
+
 def test_fused_gradient_plumbing_equals_the_separate_passes(dev):
     """hd_concat_up_bwd == hd_upsample2_bwd + hd_slice_channels and hd_maxpool3x3s2_bwd_idx_add == hd_maxpool3x3s2_bwd_idx + hd_add_f16,
     bit for bit (round 4: four launches less per decoder block pair / stem in the U-Net's backward pass)."""

@@ -1,14 +1,38 @@
-"""A/B of the multi-level RoIAlign forward (one block per RoI, hd_roi_align_ml with HD_ROI_ROWS=1) against the one-thread-per-output
-form (HD_ROI_ROWS=0) on the RoI population of one training step: 24 images at 300x300, four pyramid levels of 256 channels, 512 RoIs
-per image; the two launches of a step (16 images without gradient, 8 with).  The kernel choice is read once per process, so each leg
-runs in a child; outputs must be bit-identical.
-    python tools/bench_roi.py"""
-import os, subprocess, sys
+"""Timer of the multi-level RoIAlign forward (hd_roi_align_ml) and gather backward (hd_roi_align_ml_bwd_gather) on the RoI population
+of one training step: 24 images at 300x300, four pyramid levels of 256 channels, 512 RoIs per image; the two forward launches of a step
+(16 images without gradient, 8 with) and the backward of the 8.  Prints the three times and saves the three outputs; the kernels are
+deterministic, so the files of two builds (HD_HIP_LIB selects the library) must compare bit-identical.
+    python tools/bench_roi.py OUT.pt
+    python tools/bench_roi.py --compare A.pt B.pt"""
+import math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
 
-if len(sys.argv) > 1 and sys.argv[1] == "child":
-    import math
-    import torch
+NAMES = ("16 images (8192 RoIs)", "8 images (4096 RoIs)", "backward, 8 images")
+
+
+def compare(pa, pb):
+    same = True
+    for name, a, b in zip(NAMES, torch.load(pa), torch.load(pb)):
+        eq = a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.view(torch.int16), b.view(torch.int16))
+        same = same and eq
+        print("   %-24s bit-identical: %s  elements that differ %d  non-zero share %.3f" %
+              (name, eq, -1 if a.shape != b.shape else int((a != b).sum()), float((a != 0).float().mean())))
+    return same
+
+
+def timed(fn):
+    for _ in range(3):
+        out = fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(20):
+        out = fn()
+    e1.record(); torch.cuda.synchronize()
+    return out, e0.elapsed_time(e1) / 20 * 1e3
+
+
+def run(path):
     from hallucidet_amd import ops
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(5)
@@ -28,42 +52,24 @@ if len(sys.argv) > 1 and sys.argv[1] == "child":
     lvl = torch.floor(4 + torch.log2(torch.sqrt(area) / 224.0) + 1e-6).clamp(2, 5).to(torch.int32) - 2
     lvl = lvl.to(dev)
     outs = []
-    for (lo, hi, name) in ((0, 16 * per, "16 images (8192 RoIs)"), (16 * per, 24 * per, "8 images (4096 RoIs)")):
+    for (lo, hi, name) in ((0, 16 * per, NAMES[0]), (16 * per, 24 * per, NAMES[1])):
         r, l = rois[lo:hi].contiguous(), lvl[lo:hi].contiguous()
-        for _ in range(3):
-            o = ops.roi_align_ml(feats, scales, r, l, 7, 7, 2)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(20):
-            o = ops.roi_align_ml(feats, scales, r, l, 7, 7, 2)
-        e1.record(); torch.cuda.synchronize()
-        print("   %-24s %7.1f us" % (name, e0.elapsed_time(e1) / 20 * 1e3), flush=True)
+        o, us = timed(lambda: ops.roi_align_ml(feats, scales, r, l, 7, 7, 2))
+        print("   %-24s %7.1f us" % (name, us), flush=True)
         outs.append(o.cpu())
     # backward (gather form) of the 8 images with gradient
     r, l = rois[:8 * per].contiguous(), lvl[:8 * per].contiguous()
     dout = (torch.randn(8 * per, 7, 7, 256, generator=g) * 0.1).half().to(dev)
     shapes = [(8, s_, s_, 256) for s_ in sizes]
-    for _ in range(3):
-        dfs = ops.roi_align_ml_bwd_gather(dout, r, l, shapes, scales, 2)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(20):
-        dfs = ops.roi_align_ml_bwd_gather(dout, r, l, shapes, scales, 2)
-    e1.record(); torch.cuda.synchronize()
-    print("   %-24s %7.1f us" % ("backward, 8 images", e0.elapsed_time(e1) / 20 * 1e3), flush=True)
+    dfs, us = timed(lambda: ops.roi_align_ml_bwd_gather(dout, r, l, shapes, scales, 2))
+    print("   %-24s %7.1f us" % (NAMES[2], us), flush=True)
     outs.append(torch.cat([d.flatten() for d in dfs]).cpu())
-    torch.save(outs, sys.argv[2])
-    raise SystemExit(0)
+    torch.save(outs, path)
 
-import torch
-res = {}
-for mode in ("0", "1"):
-    print("HD_ROI_ROWS=%s" % mode, flush=True)
-    path = "/tmp/bench_roi_%s.pt" % mode
-    subprocess.run([sys.executable, os.path.abspath(__file__), "child", path], env=dict(os.environ, HD_ROI_ROWS=mode), check=True)
-    res[mode] = torch.load(path)
-for a, b in zip(res["0"], res["1"]):
-    d = (a.float() - b.float()).abs()
-    ulp = torch.maximum(a.float().abs(), b.float().abs()) * 2.0 ** -10 + 2.0 ** -24
-    print("bit-identical: %s  max |diff| %.3g  largest diff in fp16 ulps of the value %.2f  elements that differ %.2e  non-zero share %.3f" %
-          (torch.equal(a.view(torch.int16), b.view(torch.int16)), float(d.max()), float((d / ulp).max()), float((d > 0).float().mean()), float((a != 0).float().mean())))
+
+if __name__ == "__main__":
+    if len(sys.argv) == 4 and sys.argv[1] == "--compare":
+        raise SystemExit(0 if compare(sys.argv[2], sys.argv[3]) else 1)
+    if len(sys.argv) != 2 or sys.argv[1].startswith("-"):
+        raise SystemExit(__doc__)
+    run(sys.argv[1])
