@@ -27,7 +27,8 @@ def main(argv=None):
                               ext=args.ext or ".jpg", seed=args.seed, cache_units=("test",),
                               **Config.cache_kwargs(args, dev))          # only the test split is read: only its unit is cached
     kw = dict(batch_size=args.batch, model_name=args.decoder_backbone, detector_name=Config.Detector.name, precision=args.precision, device=dev,
-              loss_pixel=Config.Losses.pixel, loss_perceptual=Config.Losses.perceptual, map_device=args.map_device,
+              loss_pixel=Config.Losses.pixel, loss_perceptual=Config.Losses.perceptual, loss_structural=Config.Losses.structural,
+              map_device=args.map_device,
               ir_preprocess=args.ir_preprocess, media=media_writer(args), **Config.transform_kwargs(args))
     model = EncoderDecoderLit.load_from_checkpoint(args.hallucidet_path, strict=False, **kw) if args.hallucidet_path else EncoderDecoderLit(**kw)
     if args.detector_path:

@@ -166,6 +166,8 @@ PROTOTYPES = {
     "hd_fastrcnn_loss_masked": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp]),
     "hd_fastrcnn_loss_masked_bwd": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp]),
     "hd_pixel_loss": (C.c_int, [vp, vp, vp] + [C.c_int] * 5 + [c_f, c_f, C.c_int] + [vp] * 6),
+    "hd_ssim_loss_workspace": (c_i64, [C.c_int] * 4),
+    "hd_ssim_loss": (C.c_int, [vp, vp, vp] + [C.c_int] * 5 + [c_f, c_f] + [vp] * 5 + [c_i64, vp, vp]),
     "hd_augment_u8_ws_bytes": (c_i64, [C.c_int] * 4),
     "hd_augment_u8": (C.c_int, [vp, vp] + [C.c_int] * 4 + [vp, vp, vp]),
     "hd_batch_gather_u8": (C.c_int, [vp, c_i64, vp, C.c_int, c_i64, C.c_int, vp, vp]),

@@ -36,6 +36,7 @@ class Config:
         }
         pixel = None
         perceptual = None
+        structural = None     # --structural: 'ssim' fills the two perceptual slots (weights perceptual_rgb / perceptual_ir)
 
     class EncoderDecoder:
         in_channels_encoder = 3
@@ -145,6 +146,9 @@ class Config:
         p.add_argument("--detector-resize", type=str, default="nearest", choices=["nearest", "bilinear", "bilinear_aa"])
         p.add_argument("--detector-norm", type=str, default="none", choices=["none", "imagenet"])
         p.add_argument("--perceptual", type=str, default=None)
+        # the structural reconstruction loss (losses/losses.py: 1 - SSIM in hd_ssim_loss), weighted by --weight-perceptual-rgb / -ir into
+        # the reference's two perceptual slots; --perceptual ssim itself selects nothing, as in the reference.  Default: off
+        p.add_argument("--structural", type=str, default=None, choices=["ssim"])
         p.add_argument("--weight-perceptual-rgb", type=float, default=0.0)
         p.add_argument("--weight-perceptual-ir", type=float, default=0.0)
         p.add_argument("--weight-det-regression", type=float, default=0.1)
@@ -191,6 +195,8 @@ class Config:
             Config.Losses.pixel = args.pixel
         if args.perceptual is not None:
             Config.Losses.perceptual = args.perceptual
+        if args.structural is not None:
+            Config.Losses.structural = args.structural
         w = Config.Losses.hparams_losses_weights
         w.update(pixel_rgb=args.weight_pixel_rgb, pixel_ir=args.weight_pixel_ir, perceptual_rgb=args.weight_perceptual_rgb,
                  perceptual_ir=args.weight_perceptual_ir, det_regression=args.weight_det_regression,

@@ -191,13 +191,28 @@ class DetectorStepGraph:
                         d.flush()
             (dimg,) = torch.autograd.grad(total, x, grad_outputs=e.scale)      # = d(total * scale)/dx without the extra launches
             cur.wait_stream(branch)
+            # Two reconstruction losses at once: the eager autograd nodes hand the U-Net (pixel + structural) + detector, and fp32 addition
+            # is not associative, so the two are summed in a buffer of their own first and that is added to dimg (one more fill and
+            # one more add over the batch).  With one of them, detector + term is the same sum in either order: it goes into dimg directly
+            both = e.pixel is not None and e.structural is not None
+            sink = torch.zeros_like(dimg) if both else dimg
             if e.pixel is not None:
                 # the pixel loss (train_hallucidet.py:173-176,209): both weighted terms, total = (det_total + rgb) + ir, and their scaled
                 # gradient added into dimg -- the buffer the U-Net's backward graphs adopt -- in one launch pair
                 kind, w_rgb, w_ir = e.pixel
-                out = ops.pixel_loss(e.x, e.rgb, e.ir, kind, w_rgb, w_ir, base_total=total, gs=e.scale, dhall=dimg)
+                out = ops.pixel_loss(e.x, e.rgb, e.ir, kind, w_rgb, w_ir, base_total=total, gs=e.scale, dhall=sink)
                 losses_det = dict(losses_det, pixel_rgb=out[0], pixel_ir=out[1], det_total=total)
                 total = out[2]
+            if e.structural is not None:
+                # the structural loss in the perceptual slots (train_hallucidet.py:174,176,209), chained after the pixel terms:
+                # total = (total + rgb) + ir, its scaled gradient added next to theirs
+                _, w_rgb, w_ir = e.structural
+                sout = ops.ssim_loss(e.x, e.rgb, e.ir, w_rgb, w_ir, base_total=total, gs=e.scale, dhall=sink)
+                losses_det = dict(losses_det, perceptual_rgb=sout[0], perceptual_ir=sout[1])
+                losses_det.setdefault('det_total', total)
+                total = sout[2]
+            if both:
+                dimg.add_(sink)
             return losses_det, total, dets, dimg
 
         _eff._GRAPH_FLAGS = []
@@ -245,6 +260,9 @@ class DetectorStepGraph:
         pixel = lit.pixel_setup()                      # (kind, w_rgb, w_ir) of the pixel loss, None when off (the key is then unchanged)
         if pixel is not None:
             key = key + (pixel,)
+        structural = lit.structural_setup()            # (kind, w_rgb, w_ir) of the structural loss, None when off (the key is then unchanged)
+        if structural is not None:
+            key = key + (("structural",) + structural,)
         how = getattr(lit.detector.transform, "_how", None)   # (mode, mean, std) of --detector-resize / --detector-norm, None for the reference's
         if how is not None:
             key = key + (("resize",) + how,)
@@ -257,6 +275,7 @@ class DetectorStepGraph:
         if fresh:
             e = self._build(key, imgs_hallucinated, imgs_rgb, imgs_ir, G)
             e.pixel = pixel
+            e.structural = structural
         if e.scale_value != s:
             e.scale.fill_(s)
             e.inv_scale.fill_(1.0 / s)

@@ -1276,6 +1276,57 @@ def pixel_loss(hall, rgb, ir, kind, w_rgb, w_ir, *, base_total=None, gs=None, dh
     return out if base_total is not None else out[:2]
 
 
+SSIM_WINDOW = 11            # taps of hd_ssim_loss's Gaussian window (HD_SSIM_WINDOW)
+SSIM_TILE = (32, 32)        # rows, columns of the map one block of hd_ssim_loss covers (HD_SSIM_TILE_H, HD_SSIM_TILE_W)
+
+
+def ssim_loss(hall, rgb, ir, w_rgb, w_ir, *, base_total=None, gs=None, dhall=None, out=None, maps=None):
+    """hd_ssim_loss: -> (w_rgb * (1 - SSIM(hall, rgb)), w_ir * (1 - SSIM(hall, ir)), base_total + both, SSIM(hall, rgb), SSIM(hall, ir))
+    as one fp32 tensor of five, on the current stream; element 2 is written only when `base_total` is given.  SSIM: 11-tap Gaussian
+    window (sigma 1.5), 'valid', data range 1, mean over N*3*(H-10)*(W-10).  hall / rgb: fp32 contiguous [N, 3, H, W], H, W >= 11; ir:
+    fp32 contiguous [N, 1, H, W] (one plane against each channel) or [N, 3, H, W].  Gradient mode (`dhall`, same layout as hall):
+    dhall += gs * d(out[0] + out[1]) / d hall, `gs` a 0-dim fp32 device tensor.  `maps` (fp32 contiguous [2, N, 3, H-10, W-10]) receives
+    the two terms' index maps.  Nothing is broadcast or converted here: any other shape, dtype or layout raises."""
+    _need_cuda(hall, rgb, ir, base_total, gs, dhall, out, maps)
+    if hall.dim() != 4 or hall.shape[1] != 3:
+        raise ValueError("ssim_loss: hall must be [N, 3, H, W] (got %s)" % (tuple(hall.shape),))
+    N, _, H, W = hall.shape
+    if H < SSIM_WINDOW or W < SSIM_WINDOW:
+        raise ValueError("ssim_loss: H and W must be at least the window, %d (got %s)" % (SSIM_WINDOW, tuple(hall.shape),))
+    if tuple(rgb.shape) != tuple(hall.shape):
+        raise ValueError("ssim_loss: rgb must have hall's shape %s (got %s)" % (tuple(hall.shape), tuple(rgb.shape)))
+    if ir.dim() != 4 or ir.shape[1] not in (1, 3) or (ir.shape[0], ir.shape[2], ir.shape[3]) != (N, H, W):
+        raise ValueError("ssim_loss: ir must be [%d, 1 or 3, %d, %d] (got %s)" % (N, H, W, tuple(ir.shape)))
+    named = [("hall", hall), ("rgb", rgb), ("ir", ir)] + ([("dhall", dhall)] if dhall is not None else []) \
+        + ([("maps", maps)] if maps is not None else [])
+    for name, t in named:
+        if t.dtype != torch.float32:
+            raise TypeError("ssim_loss: %s must be float32 (got %s)" % (name, t.dtype))
+        if not t.is_contiguous():
+            raise ValueError("ssim_loss: %s must be contiguous (strides %s)" % (name, tuple(t.stride())))
+    if dhall is not None:
+        if tuple(dhall.shape) != tuple(hall.shape):
+            raise ValueError("ssim_loss: dhall must have hall's shape %s (got %s)" % (tuple(hall.shape), tuple(dhall.shape)))
+        if gs is None or gs.numel() != 1 or gs.dtype != torch.float32:
+            raise ValueError("ssim_loss: gradient mode needs gs, a one-element float32 device tensor")
+    if maps is not None and tuple(maps.shape) != (2, N, 3, H - SSIM_WINDOW + 1, W - SSIM_WINDOW + 1):
+        raise ValueError("ssim_loss: maps must be [2, %d, 3, %d, %d] (got %s)" % (N, H - SSIM_WINDOW + 1, W - SSIM_WINDOW + 1, tuple(maps.shape)))
+    if base_total is not None and (base_total.numel() != 1 or base_total.dtype != torch.float32):
+        raise ValueError("ssim_loss: base_total must be a one-element float32 device tensor")
+    if out is None:
+        out = torch.empty((5,), dtype=torch.float32, device=hall.device)
+    elif out.numel() < 5 or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("ssim_loss: out must be a contiguous float32 tensor of at least 5 elements")
+    lib = _abi.load()
+    nbytes = int(lib.hd_ssim_loss_workspace(N, H, W, 1 if dhall is not None else 0))
+    if nbytes < 0:
+        raise ValueError("ssim_loss: shape %s is outside hd_ssim_loss's range (N <= 21845)" % (tuple(hall.shape),))
+    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=hall.device)
+    check(lib.hd_ssim_loss(ptr(hall), ptr(rgb), ptr(ir), N, 3, H, W, ir.shape[1], float(w_rgb), float(w_ir), ptr(base_total), ptr(gs),
+                           ptr(dhall), ptr(maps), ptr(ws), nbytes, ptr(out), _stream()), "hd_ssim_loss")
+    return out
+
+
 AUG_ROW = 12                    # floats per image in hd_augment_u8's parameter record (HD_AUG_ROW)
 AUG_MAX_PIXELS = 16843009       # largest H*W of hd_augment_u8: its image sums are 32-bit integers (HD_AUG_MAX_PIXELS)
 

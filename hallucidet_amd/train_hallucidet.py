@@ -13,7 +13,7 @@ import torch.nn as nn
 from . import ops
 from .config import Config
 from .distributed import GradientAverager, broadcast_parameters, exchange_and_step
-from .losses.losses import PixelTerms, Reconstruction
+from .losses.losses import PixelTerms, Reconstruction, StructuralTerms
 from .models.cnnBasedThermalInfraredDA import IR_PREPROCESS_NAMES, CnnBasedThermalInfraredDA
 from .models.custom_generalized_transform import configure_transform
 from .models.detector import Detector
@@ -53,7 +53,7 @@ class EncoderDecoderLit(nn.Module):
     def __init__(self, batch_size=4, wandb_logger=None, model_name='resnet34', in_channels=3, output_channels=3, lr=0.0001,
                  loss_pixel=None, loss_perceptual=None, detector_name='fasterrcnn', train_det=False, fuse_data='none',
                  scheduler_on=False, detector=None, precision=16, device='cuda', use_graphs=True, map_device='cpu',
-                 ir_preprocess='none', media=None, resize_mode='nearest', image_mean=None, image_std=None):
+                 ir_preprocess='none', media=None, resize_mode='nearest', image_mean=None, image_std=None, loss_structural=None):
         super().__init__()
         self.model_name, self.wandb_logger = model_name, wandb_logger
         self.in_channels, self.output_channels = in_channels, output_channels
@@ -78,6 +78,8 @@ class EncoderDecoderLit(nn.Module):
         # None; LPIPS raises (the `lpips` package and its weights are not available), the other perceptual names select nothing
         self.loss_pixel = Reconstruction.select_loss_pixel(loss_pixel=loss_pixel)
         self.loss_perceptual = Reconstruction.select_loss_perceptual(loss_perceptual=loss_perceptual)
+        # --structural: 'ssim' -> the HIP structural loss (hd_ssim_loss) in the two perceptual slots; None -> off
+        self.loss_structural = Reconstruction.select_loss_structural(loss_structural)
         self.encoder_decoder = EncoderDecoder(name=self.model_name, encoder_depth=5, encoder_weights=None,
                                               decoder_attention_type=None, in_channels=self.in_channels,
                                               output_channels=self.output_channels,
@@ -155,9 +157,14 @@ class EncoderDecoderLit(nn.Module):
                 loss_pixel_rgb, loss_pixel_ir = losses_det.pop('pixel_rgb'), losses_det.pop('pixel_ir')
             else:
                 loss_pixel_rgb, loss_pixel_ir, total_loss = self._pixel_terms(imgs_hallucinated, loss_det_total, imgs_rgb, imgs_ir_three_channel)
-        for extra in (loss_perceptual_rgb, loss_perceptual_ir):
-            if torch.is_tensor(extra) or extra != 0.0:
-                total_loss = total_loss + extra
+        if self.loss_structural is not None:
+            if 'perceptual_rgb' in losses_det:      # computed inside the detector graph, chained after the pixel terms
+                if self.loss_pixel is None:
+                    loss_det_total = losses_det.pop('det_total')
+                loss_perceptual_rgb, loss_perceptual_ir = losses_det.pop('perceptual_rgb'), losses_det.pop('perceptual_ir')
+            else:
+                loss_perceptual_rgb, loss_perceptual_ir, total_loss = self._structural_terms(imgs_hallucinated, total_loss, imgs_rgb,
+                                                                                             imgs_ir_three_channel)
 
         self._last_detections = dict(hall=detections_hall, rgb=detections_rgb, ir=detections_ir)
         return {
@@ -224,6 +231,19 @@ class EncoderDecoderLit(nn.Module):
             return None
         w = Config.Losses.hparams_losses_weights
         return self.loss_pixel.kind, float(w['pixel_rgb']), float(w['pixel_ir'])
+
+    def structural_setup(self):
+        """-> (kind, w_rgb, w_ir) of the structural loss, the weights being Config's perceptual ones read at call time; None when off."""
+        if self.loss_structural is None:
+            return None
+        w = Config.Losses.hparams_losses_weights
+        return self.loss_structural.kind, float(w['perceptual_rgb']), float(w['perceptual_ir'])
+
+    def _structural_terms(self, imgs_hallucinated, base_total, imgs_rgb, imgs_ir_three_channel):
+        """train_hallucidet.py:174,176,209: (w_rgb * (1 - SSIM(rgb, hall)), w_ir * (1 - SSIM(ir3, hall)), base_total + both), one node."""
+        _, w_rgb, w_ir = self.structural_setup()
+        return StructuralTerms.apply(imgs_hallucinated, base_total.reshape(()).float(), imgs_rgb.contiguous(),
+                                     self._pixel_ir_planes(imgs_ir_three_channel), w_rgb, w_ir)
 
     @staticmethod
     def _pixel_ir_planes(imgs_ir_three_channel):

@@ -543,6 +543,27 @@ int hd_fastrcnn_loss_masked_bwd(const float* logits, const float* box_regression
  * Null hall / rgb / ir / part_ws / out, C != 3, ir_channels not in {1, 3}, kind not in {0, 1}, or dhall without gs -> HD_E_ARG. */
 int hd_pixel_loss(const float* hall, const float* rgb, const float* ir, int N, int C, int H, int W, int ir_channels, float w_rgb,
                   float w_ir, int kind, const float* base_total, const float* gs, float* dhall, float* part_ws, float* out, void* stream);
+/* Structural reconstruction loss (--structural ssim; csrc/ssim_loss.hip): SSIM of Wang et al. 2004 with an 11-tap Gaussian window
+ * (sigma 1.5, separable, 'valid': maps are Hm x Wm = (H-10) x (W-10)), data range 1, C1 = 1e-4, C2 = 9e-4.  hall, rgb, ir as for
+ * hd_pixel_loss (fp32 NCHW, contiguous, C == 3; a one-plane ir is compared against each of the three channels), H, W >= HD_SSIM_WINDOW,
+ * N <= 21845.  With S the per-position index and SSIM its mean over N*3*Hm*Wm (also for a one-plane ir):
+ *   out[0] = w_rgb * (1 - SSIM(hall, rgb)),  out[1] = w_ir * (1 - SSIM(hall, ir)),
+ *   out[2] = (base_total[0] + out[0]) + out[1]         when base_total (a device scalar) is given,
+ *   out[3] = SSIM(hall, rgb),  out[4] = SSIM(hall, ir).
+ * Gradient mode (dhall != NULL, same layout as hall): dhall += gs[0] * d(out[0] + out[1]) / d hall, gathered (one writer per element,
+ * no atomics).  maps (nullable): [2][N][3][Hm][Wm] fp32, receives the S maps of the two terms (a test hook).  ws: 16-byte aligned
+ * device memory of hd_ssim_loss_workspace(N, H, W, grad) bytes (grad = 1 when dhall is given: the block partials, and four weighted
+ * gradient planes of the batch's size in gradient mode); the query returns -1 for a shape the entry refuses.  The values are the same
+ * bits in both modes; deterministic (fixed block partials, fixed-order final sum); no host synchronisation.
+ * Null hall / rgb / ir / ws / out, C != 3, H or W < HD_SSIM_WINDOW, ir_channels not in {1, 3}, dhall without gs, or ws_bytes below
+ * the query -> HD_E_ARG. */
+#define HD_SSIM_WINDOW 11
+#define HD_SSIM_TILE_H 32   /* rows and columns of the map (forward) and of the image (gradient) one block covers */
+#define HD_SSIM_TILE_W 32
+int64_t hd_ssim_loss_workspace(int N, int H, int W, int grad);
+int hd_ssim_loss(const float* hall, const float* rgb, const float* ir, int N, int C, int H, int W, int ir_channels, float w_rgb,
+                 float w_ir, const float* base_total, const float* gs, float* dhall, float* maps, void* ws, int64_t ws_bytes, float* out,
+                 void* stream);
 /* Photometric training augmentation of the reference's detector recipe (train_detector.py:401-410: ColorJitter, RandomInvert,
  * RandomAdjustSharpness, RandomEqualize) on a planar uint8 batch, bit for bit what Pillow computes (csrc/augment.hip).
  * x, out [N][C][H][W] uint8, C = 3 (RGB) or 1 (PIL mode L), H, W >= 3, H*W <= HD_AUG_MAX_PIXELS (the image sums are 32-bit integers),

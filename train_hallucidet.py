@@ -60,7 +60,8 @@ def main(argv=None):
     kw = dict(batch_size=args.batch, model_name=args.decoder_backbone, in_channels=Config.EncoderDecoder.in_channels_encoder,
               output_channels=Config.EncoderDecoder.out_channels_decoder, lr=1e-4 if args.lr is None else args.lr,
               detector_name=Config.Detector.name, train_det=Config.Detector.train_det, fuse_data=args.fuse_data, precision=args.precision, device=dev,
-              loss_pixel=Config.Losses.pixel, loss_perceptual=Config.Losses.perceptual, map_device=args.map_device,
+              loss_pixel=Config.Losses.pixel, loss_perceptual=Config.Losses.perceptual, loss_structural=Config.Losses.structural,
+              map_device=args.map_device,
               ir_preprocess=args.ir_preprocess, media=media_writer(args, rank), **Config.transform_kwargs(args))
     model = EncoderDecoderLit.load_from_checkpoint(args.pre_train_path, strict=False, **kw) if args.pre_train_path else EncoderDecoderLit(**kw)
     if args.detector_path:
