@@ -28,7 +28,7 @@ def main(argv=None):
                               **Config.cache_kwargs(args, dev))          # only the test split is read: only its unit is cached
     kw = dict(batch_size=args.batch, model_name=args.decoder_backbone, detector_name=Config.Detector.name, precision=args.precision, device=dev,
               loss_pixel=Config.Losses.pixel, loss_perceptual=Config.Losses.perceptual, loss_structural=Config.Losses.structural,
-              map_device=args.map_device,
+              map_device=args.map_device, **Config.miss_rate_kwargs(args),
               ir_preprocess=args.ir_preprocess, media=media_writer(args), **Config.transform_kwargs(args))
     model = EncoderDecoderLit.load_from_checkpoint(args.hallucidet_path, strict=False, **kw) if args.hallucidet_path else EncoderDecoderLit(**kw)
     if args.detector_path:

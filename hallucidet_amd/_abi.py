@@ -177,6 +177,7 @@ PROTOTYPES = {
     "hd_media_render": (C.c_int, [vp, c_i64, c_i64] + [C.c_int] * 5 + [vp, C.c_int, vp, vp, C.c_int, c_f, vp, vp, C.c_int, vp, vp, vp]),
     "hd_map_match":(C.c_int, [vp] * 4 + [C.c_int] * 2 + [vp] * 3 + [C.c_int, vp, C.c_int] + [vp] * 9),
     "hd_map_accumulate": (C.c_int, [vp, vp, vp, c_i64, vp, vp, C.c_int, vp, vp, vp, vp]),
+    "hd_mr_accumulate": (C.c_int, [vp, vp, vp, c_i64, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp]),
     "hd_sample_pos_neg": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "hd_roi_postprocess": (C.c_int, [vp, vp, vp, C.c_long, vp, C.c_int, C.c_int, C.c_int, vp] + [C.c_float] * 5 + [vp] * 4),
     "hd_roi_samples_padded": (C.c_int, [vp] * 7 + [C.c_int] * 4 + [vp] * 6),

@@ -120,6 +120,11 @@ class Config:
         # where validation / test compute COCO mAP: 'cpu' = the host evaluator, 'cuda' = the HIP evaluator (same numbers; with several
         # ranks it reports the mAP of the whole split instead of the mean of the per-rank values)
         p.add_argument("--map-device", type=str, default="cpu", choices=["cpu", "cuda"])
+        # the log-average miss rate (Dollar et al. 2012; metrics/metrics.py) next to the mAP, from the same matches: validation / test
+        # report lamr, lamr_75, lamr_small / _medium / _large and mr_fppi01.  --miss-rate-curves DIR (implies --miss-rate): after the test
+        # split rank 0 writes the MR-FPPI curves as DIR/test_{stream}_class{label}.csv.  Default: off
+        p.add_argument("--miss-rate", action="store_true")
+        p.add_argument("--miss-rate-curves", type=str, default=None, metavar="DIR")
         # train_detector.py: 'reference' = the reference's photometric augmentation of the training split (train_detector.py:401-410),
         # applied to the uint8 batch on the GPU (dataloader/augment.py)
         p.add_argument("--augment", type=str, default="none", choices=["none", "reference"])
@@ -181,6 +186,11 @@ class Config:
         """The Lit modules' transform keywords from --detector-resize / --detector-norm."""
         mean, std = Config.detector_norm_stats(args.detector_norm)
         return dict(resize_mode=args.detector_resize, image_mean=mean, image_std=std)
+
+    @staticmethod
+    def miss_rate_kwargs(args):
+        """The Lit modules' miss-rate keywords from --miss-rate / --miss-rate-curves (a curve directory turns the metric on)."""
+        return dict(miss_rate=bool(args.miss_rate or args.miss_rate_curves), miss_rate_curves=args.miss_rate_curves)
 
     @staticmethod
     def cache_kwargs(args, device):

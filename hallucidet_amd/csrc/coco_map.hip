@@ -15,6 +15,21 @@
 // largest pr among the points with rc >= r: every point contributes to the bins of the recall thresholds it reaches through an LDS
 // integer max on the bits of the (non-negative) double, then a suffix max over the bins.  Max is exact and order-free, so the result
 // does not depend on scheduling.  No float atomics.
+//
+// hd_mr_accumulate: the integer half of the log-average miss rate ("LAMR", MR^-2 of Dollar et al., PAMI 2012) over the same flags and
+// the same global order; the float half (1 - hit / n_gt, the log-mean) is the host evaluator's numpy code on both paths, so device and
+// host agree by construction.  Definition (metrics/metrics.py states the same), per class k, area range a, IoU threshold t:
+//   inputs      hd_map_match's per-image results at max-dets 100 (every entry of `order`); unevaluated images contribute nothing
+//   order       the caller's global order: descending score, ties in image order then rank (the host's stable sorts)
+//   counts      tp_j = cumsum(matched & !ignored), fp_j = cumsum(!matched & !ignored); an ignored detection counts as neither
+//   images      n_img = the images passed to update(), images without a box included; n_gt = npig[k][a]
+//   undefined   n_eval[k] == 0 or n_gt == 0: -1 in every entry of the segment
+//   rates       ref [9] = the host's np.logspace(-2, 0, 9) doubles, passed in (not recomputed here)
+//   hit         fppi_j = double(fp_j) / double(n_img), an IEEE fp64 division; hit_i = max{tp_j : fppi_j <= ref[i]}, 0 when no point
+//               qualifies or the class has no detection
+//   miss rate   (host) mr_i = 1.0 - hit_i / n_gt; lamr = exp(mean(log(max(mr, 1e-10))))
+// One block per (t, k, a) with the chunked block scan of hd_map_accumulate; a counted point raises LDS bin i0 = #{i : ref[i] < fppi}
+// to its tp with an integer max (it qualifies for exactly the rates i >= i0), one thread takes the prefix max over the bins.
 #include "hd_common.h"
 
 namespace {
@@ -298,6 +313,82 @@ __global__ __launch_bounds__(AB) void map_accumulate_kernel(const int32_t* __res
   }
 }
 
+constexpr int NREF = HD_MR_NUM_REF;     // 9 reference FPPI rates
+
+__global__ __launch_bounds__(AB) void mr_accumulate_kernel(const int32_t* __restrict__ order, const int32_t* __restrict__ class_off,
+                                                           const int32_t* __restrict__ flags, int64_t nk100,
+                                                           const int32_t* __restrict__ npig, const int32_t* __restrict__ n_eval, int K,
+                                                           int n_images, const double* __restrict__ ref_fppi, int32_t* __restrict__ hit,
+                                                           int32_t* __restrict__ total, int curve_t, int32_t* __restrict__ curve_tp,
+                                                           int32_t* __restrict__ curve_fp) {
+  __shared__ double s_ref[NREF];
+  __shared__ int s_bin[NREF + 1];                  // bin c: the largest tp of the points with exactly c rates below their fppi
+  __shared__ int s_scan[AW];
+
+  // segment (t, k, a), a fastest
+  int s = blockIdx.x;
+  const int a = s % A; s /= A;
+  const int k = s % K; s /= K;
+  const int t = s;
+  const int64_t seg = ((int64_t)t * K + k) * A + a;
+  const int lo = class_off[k], hi = class_off[k + 1];
+  const bool curve = curve_tp != nullptr && t == curve_t && a == 0;
+
+  const int np_ = npig[k * A + a];
+  if (n_eval[k] == 0 || np_ == 0) {                  // no evaluated image, or no regular ground truth: undefined
+    if (threadIdx.x < NREF) hit[seg * NREF + threadIdx.x] = -1;
+    if (threadIdx.x < 2) total[seg * 2 + threadIdx.x] = -1;
+    if (curve)
+      for (int j = lo + threadIdx.x; j < hi; j += AB) {
+        curve_tp[j] = -1;
+        curve_fp[j] = -1;
+      }
+    return;
+  }
+  if (threadIdx.x < NREF) s_ref[threadIdx.x] = ref_fppi[threadIdx.x];
+  if (threadIdx.x <= NREF) s_bin[threadIdx.x] = 0;
+  __syncthreads();
+
+  const int* fl = flags + (int64_t)a * nk100;
+  const double nimg = (double)n_images;
+  int run_tp = 0, run_fp = 0;
+  for (int base = lo; base < hi; base += AB) {
+    const int j = base + threadIdx.x;
+    int packed = 0;
+    if (j < hi) {
+      const int f = fl[order[j]];
+      const bool tpb = (f >> t) & 1, igb = (f >> (T + t)) & 1;
+      packed = igb ? 0 : (tpb ? 1 : (1 << 10));        // tp | fp << 10: at most AB of either per chunk
+    }
+    int tot;
+    const int inc = block_scan(packed, s_scan, &tot);
+    const int tp = run_tp + (inc & 1023), fp = run_fp + ((inc >> 10) & 1023);
+    if (curve && j < hi) {                             // an ignored detection repeats the pair before it
+      curve_tp[j] = tp;
+      curve_fp[j] = fp;
+    }
+    if (packed) {
+      const double fppi = (double)fp / nimg;
+      int i0 = 0;
+#pragma unroll
+      for (int i = 0; i < NREF; ++i) i0 += s_ref[i] < fppi ? 1 : 0;
+      atomicMax(&s_bin[i0], tp);
+    }
+    run_tp += tot & 1023;
+    run_fp += (tot >> 10) & 1023;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int h = 0;
+    for (int i = 0; i < NREF; ++i) {
+      h = s_bin[i] > h ? s_bin[i] : h;
+      hit[seg * NREF + i] = h;
+    }
+    total[seg * 2] = run_tp;
+    total[seg * 2 + 1] = run_fp;
+  }
+}
+
 }  // namespace
 
 extern "C" int hd_map_match(const double* det_boxes, const double* det_scores, const int64_t* det_labels, const int32_t* det_count, int N,
@@ -325,6 +416,24 @@ extern "C" int hd_map_accumulate(const int32_t* order, const int32_t* class_off,
   if (K == 0) return HD_OK;
   hipLaunchKernelGGL(map_accumulate_kernel, dim3((unsigned)(T * K * A * M)), dim3(AB), 0, (hipStream_t)stream, order, class_off, flags, nk100,
                      npig, n_eval, K, rec_thrs, precision, recall);
+  HD_CHECK_LAUNCH();
+  return HD_OK;
+}
+
+extern "C" int hd_mr_accumulate(const int32_t* order, const int32_t* class_off, const int32_t* flags, int64_t nk100, const int32_t* npig,
+                                const int32_t* n_eval, int K, int n_images, const double* ref_fppi, int32_t* hit, int32_t* total,
+                                int curve_t, int32_t* curve_tp, int32_t* curve_fp, void* stream) {
+  HD_CHECK_ARG(class_off && flags && npig && n_eval && ref_fppi && hit && total, "hd_mr_accumulate: null pointer");
+  HD_CHECK_ARG(K >= 0 && nk100 >= 0 && n_images >= 0, "hd_mr_accumulate: bad sizes K=%d n_images=%d", K, n_images);
+  HD_CHECK_ARG(curve_t < T, "hd_mr_accumulate: curve threshold index %d outside [0, %d)", curve_t, T);
+  HD_CHECK_ARG(curve_t < 0 || ((curve_tp != nullptr) == (curve_fp != nullptr)), "hd_mr_accumulate: one curve buffer without the other");
+  if (K == 0) return HD_OK;
+  HD_CHECK_ARG(n_images >= 1, "hd_mr_accumulate: %d classes but no image", K);
+  HD_CHECK_ARG((int64_t)T * K * A <= INT32_MAX, "hd_mr_accumulate: too many segments (K=%d)", K);
+  const bool curve = curve_t >= 0 && curve_tp && curve_fp;
+  hipLaunchKernelGGL(mr_accumulate_kernel, dim3((unsigned)(T * K * A)), dim3(AB), 0, (hipStream_t)stream, order, class_off, flags, nk100, npig,
+                     n_eval, K, n_images, ref_fppi, hit, total, curve ? curve_t : -1, curve ? curve_tp : nullptr,
+                     curve ? curve_fp : nullptr);
   HD_CHECK_LAUNCH();
   return HD_OK;
 }

@@ -24,6 +24,11 @@ def is_dist():
     return dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or os.environ.get("HD_FORCE_DIST") == "1")
 
 
+def get_rank():
+    """This process's rank; 0 without a process group."""
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+
+
 def broadcast_parameters(flat_params, buffers=()):
     """DDP start-up semantics: rank 0's parameters and BatchNorm buffers everywhere."""
     if not is_dist():

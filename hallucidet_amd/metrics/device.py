@@ -6,6 +6,8 @@ update() keeps device tensors only and never waits for the GPU: detections arriv
 its padded tensors through `padded()`; a list of dicts is padded here with shapes the host already knows), converted to the host
 evaluator's types (fp64 boxes and scores, int64 labels).  compute() evaluates everything in two launches plus one stable sort, copies
 the precision / recall arrays to the host and runs the host evaluator's own summary code on them, so every key comes out identical.
+With `miss_rate=True` a third launch (hd_mr_accumulate) counts the log-average miss rate's integers from the same flags and order; the
+float summary and the curves of miss_rate_curves() are again the host evaluator's code.
 
 Ranks: when torch.distributed runs with more than one process, compute() gathers every rank's state (sizes first, then one padded
 byte payload) and evaluates the union in rank order, so every rank returns the same global numbers; the result is then a
@@ -145,28 +147,30 @@ def state_from_lists(preds, target, device):
 
 
 class _Summary(MeanAveragePrecision):
-    """The host evaluator's compute() over precomputed precision / recall arrays: the same class list, means, keys and dtypes."""
+    """The host evaluator's compute() over precomputed precision / recall arrays (and, with `mr`, the integer miss-rate arrays
+    (hit, total, npig, n_img) of hd_mr_accumulate): the same class list, means, keys and dtypes."""
 
-    def __init__(self, classes, precision, recall, class_metrics):
-        super().__init__(class_metrics=class_metrics)
+    def __init__(self, classes, precision, recall, class_metrics, mr=None):
+        super().__init__(class_metrics=class_metrics, miss_rate=mr is not None)
         self._gts = [{"labels": np.asarray(classes, dtype=np.int64)}]      # compute() takes its class list from the labels seen
-        self._pr = (precision, recall)
+        self._pr, self._mr_in = (precision, recall), mr
 
     def _accumulate(self, classes):
+        self._mr = self._mr_in
         return self._pr
 
 
 class DeviceMeanAveragePrecision(MeanAveragePrecision):
     """`MeanAveragePrecision` whose state and evaluation live on `device` (a GPU)."""
 
-    def __init__(self, box_format: str = "xyxy", class_metrics: bool = False, device="cuda"):
+    def __init__(self, box_format: str = "xyxy", class_metrics: bool = False, device="cuda", miss_rate: bool = False):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError("DeviceMeanAveragePrecision runs on a GPU (got %s); the host evaluator is MeanAveragePrecision" % self.device)
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.is_global = False
-        super().__init__(box_format=box_format, class_metrics=class_metrics)
+        super().__init__(box_format=box_format, class_metrics=class_metrics, miss_rate=miss_rate)
 
     def to(self, device):
         d = torch.device(device)
@@ -176,6 +180,7 @@ class DeviceMeanAveragePrecision(MeanAveragePrecision):
 
     def reset(self):
         self._chunks = []
+        self._mr = self._mr_curves = None
 
     # ------------------------------------------------------------------ update
     def update(self, preds, target):
@@ -208,6 +213,7 @@ class DeviceMeanAveragePrecision(MeanAveragePrecision):
             st = state_from_lists(preds, target, self.device)
         if n:
             self._chunks.append(st)
+            self._mr = self._mr_curves = None
 
     def state(self):
         """This evaluator's images as one state (padded tensors on the device)."""
@@ -219,11 +225,13 @@ class DeviceMeanAveragePrecision(MeanAveragePrecision):
             st = o.state() if isinstance(o, DeviceMeanAveragePrecision) else o
             if st["dc"].shape[0]:
                 self._chunks.append({k: v.to(self.device) for k, v in st.items()})
+                self._mr = self._mr_curves = None
         return self
 
     # ------------------------------------------------------------------ evaluation
     def _evaluate(self, st):
-        """-> (classes, precision [T,R,K,A,M], recall [T,K,A,M]) as the host's _accumulate returns them."""
+        """-> (classes, precision [T,R,K,A,M], recall [T,K,A,M]) as the host's _accumulate returns them; with miss_rate it also leaves
+        the host's integer miss-rate arrays in self._mr and the curve counts in self._mr_curves."""
         from .. import ops
         T, R, A, M = len(self.IOU_THRS), len(self.REC_THRS), len(self.AREA_RNG), len(self.MAX_DETS)
         assert (T, R, A, M) == (ops.MAP_NUM_IOU, ops.MAP_NUM_REC, ops.MAP_NUM_AREA, ops.MAP_NUM_MAXDET) and self.MAX_DETS == (1, 10, 100)
@@ -236,6 +244,10 @@ class DeviceMeanAveragePrecision(MeanAveragePrecision):
         classes = torch.unique(torch.cat([st["dl"][dmask], st["gl"][gmask]]), sorted=True)
         K = int(classes.numel())
         if K == 0:
+            if self.miss_rate:
+                self._mr = (-np.ones((T, 0, A, len(self.REF_FPPI)), dtype=np.int32), -np.ones((T, 0, A, 2), dtype=np.int32),
+                            np.zeros((0, A), dtype=np.int32), N)
+                self._mr_curves = (N, {})
             return [], -np.ones((T, R, 0, A, M)), -np.ones((T, 0, A, M))
         f64 = lambda v: torch.tensor(np.asarray(v, dtype=np.float64), device=dev)
         iou_start = f64([min(t, 1 - 1e-10) for t in self.IOU_THRS])
@@ -263,9 +275,32 @@ class DeviceMeanAveragePrecision(MeanAveragePrecision):
         class_off[1:] = torch.cumsum(torch.bincount(cls_of, minlength=K), 0)
         npig = npos.view(N, K, A).sum(0, dtype=torch.int64).to(torch.int32)
         n_eval = evald.view(N, K).sum(0, dtype=torch.int64).to(torch.int32)
-        precision, recall = ops.map_accumulate(idx.to(torch.int32), class_off.to(torch.int32), flags, npig, n_eval,
-                                               f64(self.REC_THRS))
+        order, class_off = idx.to(torch.int32), class_off.to(torch.int32)
+        precision, recall = ops.map_accumulate(order, class_off, flags, npig, n_eval, f64(self.REC_THRS))
+        if self.miss_rate:
+            # the same flags and the same order at max-dets 100; the integers go through the host's own summary code
+            hit, total, (ctp, cfp) = ops.mr_accumulate(order, class_off, flags, npig, n_eval, N, f64(self.REF_FPPI), curve_t=0)
+            npig_h, labels = npig.cpu().numpy(), classes.tolist()
+            self._mr = (hit.cpu().numpy(), total.cpu().numpy(), npig_h, N)
+            sc = score[idx]
+
+            def curves():                                   # the per-detection arrays leave the GPU only when the curves are asked for
+                s, tp, fp, off, n_ev = sc.cpu().numpy(), ctp.cpu().numpy(), cfp.cpu().numpy(), class_off.tolist(), n_eval.tolist()
+                return N, {c: (s[off[k]:off[k + 1]], tp[off[k]:off[k + 1]], fp[off[k]:off[k + 1]], int(npig_h[k, 0]))
+                           for k, c in enumerate(labels) if n_ev[k] and npig_h[k, 0] > 0}
+            self._mr_curves = curves
         return classes.tolist(), precision.cpu().numpy(), recall.cpu().numpy()
+
+    def miss_rate_curves(self):
+        """As the host evaluator's, from hd_mr_accumulate's cumulative counts and the scores in the global order.  Under
+        torch.distributed the curves cover the whole split; call compute() first (on every rank: it gathers), then this on any rank."""
+        if not self.miss_rate:
+            raise ValueError("miss_rate_curves() needs an evaluator built with miss_rate=True")
+        if self._mr_curves is None:
+            self.compute()
+        if callable(self._mr_curves):
+            self._mr_curves = self._mr_curves()
+        return super().miss_rate_curves()
 
     def compute(self):
         from ..distributed import is_dist
@@ -275,6 +310,7 @@ class DeviceMeanAveragePrecision(MeanAveragePrecision):
             if glob:
                 st = merge_states(gather_states(st))
             classes, precision, recall = self._evaluate(st)
-        out = _Summary(classes, precision, recall, self.class_metrics).compute()
+        self._mr_classes = list(classes)
+        out = _Summary(classes, precision, recall, self.class_metrics, mr=self._mr if self.miss_rate else None).compute()
         self.is_global = glob
         return GlobalResult(out) if glob else out

@@ -1647,6 +1647,7 @@ def media_render_host(x, mode, det=None, gt=None, threshold=0.5, nrow=8):
 # COCO mAP evaluation grid of hd_map_match / hd_map_accumulate (include/hallucidet_hip.h)
 MAP_NUM_IOU, MAP_NUM_AREA, MAP_NUM_MAXDET, MAP_NUM_REC = 10, 4, 3, 101
 MAP_MAX_DET, MAP_DET_CAP, MAP_GT_CAP = 100, 1024, 512
+MR_NUM_REF = 9          # reference FPPI rates of hd_mr_accumulate
 
 
 def _need(t, dtype, shape, name, what):
@@ -1708,3 +1709,34 @@ def map_accumulate(order, class_off, flags, npig, n_eval, rec_thrs):
     check(_abi.load().hd_map_accumulate(ptr(order), ptr(class_off), ptr(flags), flags.shape[1], ptr(npig), ptr(n_eval), K, ptr(rec_thrs),
                                         ptr(precision), ptr(recall), _stream()), "hd_map_accumulate")
     return precision, recall
+
+
+def mr_accumulate(order, class_off, flags, npig, n_eval, n_images, ref_fppi, curve_t=-1):
+    """hd_mr_accumulate: the integer half of the log-average miss rate over map_accumulate's arguments (order [L] i32, class_off [K+1]
+    i32, flags [4, N*K*100] i32, npig [K, 4] i32, n_eval [K] i32), n_images = the images evaluated, ref_fppi [9] f64 ascending.
+    -> (hit [10, K, 4, 9] i32, total [10, K, 4, 2] i32, curve) on the GPU; -1 where a segment is undefined.  curve_t >= 0: curve =
+    (cum_tp [L], cum_fp [L]) i32 at IoU threshold index curve_t, area all, per position of `order`; else None.  No host sync."""
+    _need_cuda(order, class_off, flags, npig, n_eval, ref_fppi)
+    K = n_eval.shape[0]
+    w = "mr_accumulate"
+    _need(order, torch.int32, (order.shape[0],), "order", w)
+    _need(class_off, torch.int32, (K + 1,), "class_off", w)
+    _need(flags, torch.int32, (MAP_NUM_AREA, flags.shape[1] if flags.dim() == 2 else -1), "flags", w)
+    _need(npig, torch.int32, (K, MAP_NUM_AREA), "npig", w)
+    _need(n_eval, torch.int32, (K,), "n_eval", w)
+    _need(ref_fppi, torch.float64, (MR_NUM_REF,), "ref_fppi", w)
+    n_images, curve_t = int(n_images), int(curve_t)
+    if n_images < 0 or (K > 0 and n_images < 1) or flags.shape[1] % MAP_MAX_DET or (K > 0 and flags.shape[1] != n_images * K * MAP_MAX_DET):
+        raise ValueError("%s: flags of %d entries per area do not belong to %d images x %d classes" % (w, flags.shape[1], n_images, K))
+    if curve_t >= MAP_NUM_IOU:
+        raise ValueError("%s: curve_t %d outside [0, %d)" % (w, curve_t, MAP_NUM_IOU))
+    dev = n_eval.device
+    hit = torch.empty((MAP_NUM_IOU, K, MAP_NUM_AREA, MR_NUM_REF), dtype=torch.int32, device=dev)
+    total = torch.empty((MAP_NUM_IOU, K, MAP_NUM_AREA, 2), dtype=torch.int32, device=dev)
+    curve = None
+    if curve_t >= 0:
+        curve = (torch.empty((order.shape[0],), dtype=torch.int32, device=dev), torch.empty((order.shape[0],), dtype=torch.int32, device=dev))
+    check(_abi.load().hd_mr_accumulate(ptr(order), ptr(class_off), ptr(flags), flags.shape[1], ptr(npig), ptr(n_eval), K, n_images,
+                                       ptr(ref_fppi), ptr(hit), ptr(total), curve_t, ptr(curve[0]) if curve else None,
+                                       ptr(curve[1]) if curve else None, _stream()), "hd_mr_accumulate")
+    return hit, total, curve

@@ -27,13 +27,17 @@ from .utils.utils import Utils
 class DetectorLit:
     def __init__(self, batch_size=4, wandb_logger=None, lr=0.0001, detector_name='fasterrcnn', pretrained=True, optimizer_name='adam',
                  modality=None, directly_coco=False, detector=None, device='cuda', loss_scale=1024.0, precision=16, map_device='cpu',
-                 ir_preprocess='none', media=None, resize_mode='nearest', image_mean=None, image_std=None):
+                 ir_preprocess='none', media=None, resize_mode='nearest', image_mean=None, image_std=None, miss_rate=False,
+                 miss_rate_curves=None):
         if not any(k in detector_name for k in ('fasterrcnn', 'retinanet', 'fcos')):
             raise ValueError("unknown detector %r (fasterrcnn / retinanet / fcos)" % (detector_name,))
         self.wandb_logger, self.lr, self.batch_size = wandb_logger, lr, batch_size
         self.optimizer_name, self.detector_name, self.modality = optimizer_name, detector_name, modality
         self.dev = device
         self.map_device = map_device          # 'cpu': host COCO mAP evaluator (default); 'cuda': the HIP one (metrics/device.py)
+        # --miss-rate: the accumulator also reports the log-average miss rate; --miss-rate-curves DIR: rank 0 writes the test split's curves
+        self.miss_rate_curves = miss_rate_curves
+        self.miss_rate = bool(miss_rate or miss_rate_curves)
         # image-space baseline (models/cnnBasedThermalInfraredDA.py) applied to the image batch of all three splits: fine-tuning on
         # pre-processed IR, the baseline HalluciDet is compared against
         if ir_preprocess not in IR_PREPROCESS_NAMES:
@@ -164,14 +168,19 @@ class DetectorLit:
         store = self.__dict__.setdefault("_map_metrics", {})
         if split not in store:
             dev = self.dev if (torch.device(self.map_device).type == "cuda" and torch.device(self.dev).type == "cuda") else self.map_device
-            store[split] = Detection(device=dev, class_metrics=True).map      # train_detector.py:115-116
+            store[split] = Detection(device=dev, class_metrics=True, miss_rate=self.miss_rate).map      # train_detector.py:115-116
         return store[split]
 
     def _epoch_end(self, split):
         from .metrics.device import carry_global
+        from .distributed import get_rank
+        from .metrics import MeanAveragePrecision, write_miss_rate_curves
         m = self._metric(split)
         r = m.compute()
-        out = carry_global(r, Utils.filter_dictionary(r, {'map_50', 'map_75', 'map', 'map_per_class'}))
+        keys = {'map_50', 'map_75', 'map', 'map_per_class'} | (set(MeanAveragePrecision.MR_KEYS) if self.miss_rate else set())
+        out = carry_global(r, Utils.filter_dictionary(r, keys))
+        if split == 'test' and self.miss_rate_curves and get_rank() == 0:
+            write_miss_rate_curves(m, self.miss_rate_curves, 'test', 'det')
         m.reset()
         return out
 

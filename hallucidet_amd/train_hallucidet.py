@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from . import ops
 from .config import Config
-from .distributed import GradientAverager, broadcast_parameters, exchange_and_step
+from .distributed import GradientAverager, broadcast_parameters, exchange_and_step, get_rank
 from .losses.losses import PixelTerms, Reconstruction, StructuralTerms
 from .models.cnnBasedThermalInfraredDA import IR_PREPROCESS_NAMES, CnnBasedThermalInfraredDA
 from .models.custom_generalized_transform import configure_transform
@@ -53,7 +53,8 @@ class EncoderDecoderLit(nn.Module):
     def __init__(self, batch_size=4, wandb_logger=None, model_name='resnet34', in_channels=3, output_channels=3, lr=0.0001,
                  loss_pixel=None, loss_perceptual=None, detector_name='fasterrcnn', train_det=False, fuse_data='none',
                  scheduler_on=False, detector=None, precision=16, device='cuda', use_graphs=True, map_device='cpu',
-                 ir_preprocess='none', media=None, resize_mode='nearest', image_mean=None, image_std=None, loss_structural=None):
+                 ir_preprocess='none', media=None, resize_mode='nearest', image_mean=None, image_std=None, loss_structural=None,
+                 miss_rate=False, miss_rate_curves=None):
         super().__init__()
         self.model_name, self.wandb_logger = model_name, wandb_logger
         self.in_channels, self.output_channels = in_channels, output_channels
@@ -65,6 +66,10 @@ class EncoderDecoderLit(nn.Module):
         self.dev = torch.device(device)
         # where the COCO mAP accumulators live: 'cpu' = the host evaluator (default), 'cuda' = the HIP one (metrics/device.py)
         self.map_device = map_device
+        # --miss-rate: the accumulators also report the log-average miss rate (metrics/metrics.py); --miss-rate-curves DIR: rank 0 writes
+        # the test split's MR-FPPI curves there, one CSV per stream and class
+        self.miss_rate_curves = miss_rate_curves
+        self.miss_rate = bool(miss_rate or miss_rate_curves)
         # image-space baseline (models/cnnBasedThermalInfraredDA.py) applied to what the IR detector pass ("RGB Detector on IR") reads in
         # validation and test; the U-Net input, the hallucinated pass, the pixel loss and the whole training step never see it
         if ir_preprocess not in IR_PREPROCESS_NAMES:
@@ -301,7 +306,7 @@ class EncoderDecoderLit(nn.Module):
         store = self.__dict__.setdefault("_map_metrics", {})
         if split not in store:
             dev = self.dev if (torch.device(self.map_device).type == "cuda" and self.dev.type == "cuda") else self.map_device
-            store[split] = {k: Detection(device=dev).map for k in ("hall", "rgb", "ir")}
+            store[split] = {k: Detection(device=dev, miss_rate=self.miss_rate).map for k in ("hall", "rgb", "ir")}
         return store[split]
 
     def _eval_step(self, batch, batch_idx, split):
@@ -336,11 +341,15 @@ class EncoderDecoderLit(nn.Module):
 
     def _epoch_end(self, split):
         from .metrics.device import carry_global
+        from .metrics import MeanAveragePrecision, write_miss_rate_curves
         m = self._metrics(split)
+        keys = {'map_50', 'map_75', 'map'} | (set(MeanAveragePrecision.MR_KEYS) - {'lamr_per_class'} if self.miss_rate else set())
         out = {}
         for k in ("rgb", "hall", "ir"):
-            r = m[k].compute()
-            out["map_" + k] = carry_global(r, Utils.filter_dictionary(r, {'map_50', 'map_75', 'map'}))
+            r = m[k].compute()                              # every rank: the device evaluator gathers
+            out["map_" + k] = carry_global(r, Utils.filter_dictionary(r, keys))
+            if split == 'test' and self.miss_rate_curves and get_rank() == 0:
+                write_miss_rate_curves(m[k], self.miss_rate_curves, 'test', k)
         for v in m.values():
             v.reset()
         return out

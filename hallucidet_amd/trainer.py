@@ -85,9 +85,15 @@ class Trainer:
         return out
 
     @staticmethod
+    def _no_data(key, value):
+        """NaN, or the accumulators' -1 under one of their keys (map* / mar* as before, and the miss-rate keys, which DetectorLit
+        reports flat: lamr, lamr_75, lamr_small / _medium / _large, mr_fppi01; EncoderDecoderLit's are map_{stream}/...)."""
+        return math.isnan(value) or (value == -1.0 and (key.startswith("map") or key.rsplit("/", 1)[-1].startswith(("lamr", "mr_fppi"))))
+
+    @staticmethod
     def _nanmean_over_ranks(metrics, passthrough=()):
         """All monitored scalars in ONE unconditional all-reduce: per key a (sum, count) pair, NaN / 'no data' (-1 from the mAP
-        accumulators) entries contribute (0, 0).  Every rank issues the same collective whatever its local values are -- a
+        accumulators, `_no_data`) entries contribute (0, 0).  Every rank issues the same collective whatever its local values are -- a
         per-key reduce guarded by a local NaN test would pair up differently on ranks whose values differ.  Keys in `passthrough`
         (global results, identical on every rank; every rank names the same ones) are returned as they are."""
         from .distributed import is_dist
@@ -97,7 +103,7 @@ class Trainer:
         for k in keys:
             v = metrics[k]
             s, c = (float(v[0]), float(v[1])) if isinstance(v, tuple) else (float(v), 1.0)
-            if math.isnan(s) or (k.startswith("map") and s == -1.0):
+            if Trainer._no_data(k, s):
                 s, c = 0.0, 0.0
             pairs += [s, c]
         if is_dist():

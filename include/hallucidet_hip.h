@@ -688,6 +688,18 @@ int hd_map_match(const double* det_boxes, const double* det_scores, const int64_
  * image was evaluated or npig == 0, recall 0 for an empty curve).  Deterministic: integer scans and integer max only. */
 int hd_map_accumulate(const int32_t* order, const int32_t* class_off, const int32_t* flags, int64_t nk100, const int32_t* npig,
                       const int32_t* n_eval, int K, const double* rec_thrs, double* precision, double* recall, void* stream);
+/* Integer half of the log-average miss rate (Dollar et al., PAMI 2012; definition in csrc/coco_map.hip and metrics/metrics.py), one block
+ * per (threshold t, class k, area a) over hd_map_accumulate's order / class_off / flags / nk100 / npig / n_eval at max-dets 100.
+ * n_images = images passed to update(); ref_fppi [9] f64 = the host's np.logspace(-2, 0, 9), ascending.  Writes hit [10][K][4][9] i32 =
+ * max cumulative tp among the non-ignored points with double(fp) / double(n_images) <= ref_fppi[i] (0 when none) and total [10][K][4][2]
+ * i32 = the final (tp, fp); -1 in every entry of a segment with n_eval[k] == 0 or npig[k][a] == 0.  With curve_t >= 0 and both curve
+ * buffers (i32, the length of `order`) given, block (curve_t, k, area 0) also writes the inclusive cumulative tp / fp at every position
+ * of its class segment (an ignored detection repeats the pair before it; -1 for an undefined segment).  Deterministic: integer scans
+ * and integer max only; no host sync.  Caps: those of hd_map_match. */
+#define HD_MR_NUM_REF 9
+int hd_mr_accumulate(const int32_t* order, const int32_t* class_off, const int32_t* flags, int64_t nk100, const int32_t* npig,
+                     const int32_t* n_eval, int K, int n_images, const double* ref_fppi, int32_t* hit, int32_t* total, int curve_t,
+                     int32_t* curve_tp, int32_t* curve_fp, void* stream);
 /* BalancedPositiveNegativeSampler [EXT] for N images (reached from src/utils/eval_forward_fasterrcnn.py:90,127): labels [N][A]
  * i64 (>= 1 positive, 0 negative, < 0 ignored), keys [N][A] i32 >= 0 = one random key per candidate.  Per image
  * num_pos = min(#pos, cap_pos), num_neg = min(#neg, batch_size - num_pos); pos_sel / neg_sel [N][A] u8 mark the num_pos /

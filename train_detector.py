@@ -34,7 +34,7 @@ def main(argv=None):
                                seed=args.seed, rank=rank, world_size=world, modality=args.modality, **Config.cache_kwargs(args, dev))
     kw = dict(batch_size=args.batch, lr=1e-4 if args.lr is None else args.lr, detector_name=Config.Detector.name, pretrained=args.pretrained,
               modality=args.modality, directly_coco=args.directly_coco, device=dev, precision=args.precision,
-              map_device=args.map_device, ir_preprocess=args.ir_preprocess, **Config.transform_kwargs(args))
+              map_device=args.map_device, ir_preprocess=args.ir_preprocess, **Config.transform_kwargs(args), **Config.miss_rate_kwargs(args))
     if args.save_media:
         from hallucidet_amd.utils.media import MediaWriter
         kw["media"] = MediaWriter(args.save_media, every=args.media_every, offset=1, threshold=args.threshold, max_batches=args.media_max,
@@ -51,7 +51,10 @@ def main(argv=None):
                  train_augment=augment)
     tr.fit(model, dm)
     if rank == 0:
-        print("test:", {k: (v.tolist() if torch.is_tensor(v) else v) for k, v in tr.test(model, dm).items()})
+        res = tr.test(model, dm)
+        print("test:", {k: (v.tolist() if torch.is_tensor(v) else v) for k, v in res.items()})
+        if "lamr" in res:
+            print("mAP: %.2f  AP@50: %.2f  LAMR: %.2f" % tuple(round(float(res[k]) * 100, 2) for k in ("map", "map_50", "lamr")))
     if model.media is not None:
         model.media.close()
     if world > 1:

@@ -17,13 +17,13 @@ from hallucidet_amd.trainer import Trainer
 
 def print_ap50(maps, ir_preprocess=None):
     """`ir_preprocess`: the --ir-preprocess name the IR pass ran with; named on its line (None / 'none': the reference's three lines)."""
-    g = lambda k: round(float(maps[k]["map_50"]) * 100, 2)
-    if ir_preprocess in (None, "none"):
-        print("RGB Detector on IR  AP@50: ", g("map_ir"))
-    else:
-        print("RGB Detector on IR (%s) AP@50: " % ir_preprocess, g("map_ir"))
-    print("RGB Detector on RGB AP@50: ", g("map_rgb"))
-    print("HalluciDet   on IR  AP@50: ", g("map_hall"))
+    g = lambda k, key="map_50": round(float(maps[k][key]) * 100, 2)
+    ir = "RGB Detector on IR " if ir_preprocess in (None, "none") else "RGB Detector on IR (%s)" % ir_preprocess
+    # --miss-rate: under each AP@50 line the log-average miss rate of the same stream, in percent
+    for name, k in ((ir, "map_ir"), ("RGB Detector on RGB", "map_rgb"), ("HalluciDet   on IR ", "map_hall")):
+        print(name + " AP@50: ", g(k))
+        if "lamr" in maps[k]:
+            print(name + " LAMR: ", g(k, "lamr"))
 
 
 def media_writer(args, rank=0):
@@ -61,7 +61,7 @@ def main(argv=None):
               output_channels=Config.EncoderDecoder.out_channels_decoder, lr=1e-4 if args.lr is None else args.lr,
               detector_name=Config.Detector.name, train_det=Config.Detector.train_det, fuse_data=args.fuse_data, precision=args.precision, device=dev,
               loss_pixel=Config.Losses.pixel, loss_perceptual=Config.Losses.perceptual, loss_structural=Config.Losses.structural,
-              map_device=args.map_device,
+              map_device=args.map_device, **Config.miss_rate_kwargs(args),
               ir_preprocess=args.ir_preprocess, media=media_writer(args, rank), **Config.transform_kwargs(args))
     model = EncoderDecoderLit.load_from_checkpoint(args.pre_train_path, strict=False, **kw) if args.pre_train_path else EncoderDecoderLit(**kw)
     if args.detector_path:
