@@ -1,6 +1,8 @@
 // Fused optimizer step over a flat fp32 parameter arena: unscale -> clip_grad_value_ -> Adam.
 // Reference semantics: torch.optim.Adam (config.py:204-245, train_hallucidet.py:431-435) with
 // Lightning's gradient_clip_val=0.5 / algorithm "value" (train_hallucidet.py:498-499) applied first.
+#include <float.h>
+
 #include "hd_common.h"
 
 namespace {
@@ -41,11 +43,14 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
   }
 }
 
+// found[0] = 1 iff some g[i] is not finite -- torch.isfinite's rule, the one GradScaler's unscale step applies: +-inf and every NaN are
+// reported, every finite value up to and including +-FLT_MAX is not.  !(|x| <= FLT_MAX) is false for NaN operands as well; the library is
+// built without fast-math (build.py FLAGS), so the comparison is not folded away.  The flag is only ever set, never cleared.
 __global__ void check_finite_kernel(const float* __restrict__ g, int64_t n, float* found) {
   bool bad = false;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     float x = g[i];
-    if (!(fabsf(x) <= 3.0e38f)) bad = true;
+    if (!(fabsf(x) <= FLT_MAX)) bad = true;
   }
   if (__any(bad) && (threadIdx.x & 63) == 0) found[0] = 1.f;
 }

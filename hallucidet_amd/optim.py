@@ -113,6 +113,10 @@ class FusedAdam(torch.optim.Optimizer):
 
 
 class LossScaler:
+    """torch.cuda.amp.GradScaler's policy over the flat gradient arena.  Overflow rule: a step is skipped iff some gradient element is not
+    finite in torch.isfinite's sense (+-inf or NaN), which is what hd_check_finite reports; a finite gradient of any size, +-FLT_MAX
+    included, is a clean step."""
+
     def __init__(self, unet, init_scale=2.0 ** 16, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, enabled=True):
         self.runner = unet if isinstance(unet, ParamArena) else unet.runner
         self.scale_value = float(init_scale) if enabled else 1.0
