@@ -12,7 +12,7 @@
 // result does not depend on the order of arrival.  255 * H*W must fit in 32 bits: H*W <= HD_AUG_MAX_PIXELS.
 // Float steps follow Pillow's C code operation by operation: every product and sum below is one rounding (no contraction), the
 // quotients are correctly rounded, and the doubles of the hue conversion are doubles.
-#include "hd_common.h"
+#include "hd_block.h"
 #pragma clang fp contract(off)
 
 namespace {
@@ -205,10 +205,7 @@ __global__ __launch_bounds__(AB) void aug_sum_kernel(const uint8_t* __restrict__
 #pragma unroll
     for (int k = 0; k < V; ++k) acc += (uint32_t)(C == 3 ? luma(v[0][k], v[C > 1 ? 1 : 0][k], v[C > 2 ? 2 : 0][k]) : v[0][k]);
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
-  __syncthreads();
+  hd_block_put(hd_wave_reduce(acc, HdSum()), sm);
   if (threadIdx.x == 0) {
     uint32_t t = 0u;
 #pragma unroll
@@ -342,11 +339,7 @@ __global__ __launch_bounds__(AB) void aug_equalize_kernel(uint8_t* __restrict__ 
     }
     // last non-empty bin and number of non-empty bins
     int last = h ? i : -1, cnt = h ? 1 : 0;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-      last = max(last, __shfl_xor(last, d));
-      cnt += __shfl_xor(cnt, d);
-    }
+    hd_wave_reduce2(last, HdMax(), cnt, HdSum());
     if ((i & 63) == 0) {
       red[0][i >> 6] = last;
       red[1][i >> 6] = cnt;
@@ -407,7 +400,6 @@ void launch_c(bool vec_plane, bool vec_row, hipStream_t s, const uint8_t* x, con
 }
 
 inline size_t round256(size_t v) { return (v + 255) & ~(size_t)255; }
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool shape_ok(int N, int C, int H, int W) {
   return N > 0 && N <= 65535 && (C == 1 || C == 3) && H >= 3 && W >= 3 && (int64_t)H * W <= HD_AUG_MAX_PIXELS;
 }
@@ -427,7 +419,7 @@ extern "C" int hd_augment_u8(const uint8_t* x, const float* params, int N, int C
   HD_CHECK_ARG(x && params && out && ws, "hd_augment_u8: null pointer (x, params, out and ws are required)");
   HD_CHECK_ARG(shape_ok(N, C, H, W), "hd_augment_u8: need 1 <= N <= 65535, C in {1, 3}, H, W >= 3, H*W <= %d (got N=%d C=%d H=%d W=%d)",
                HD_AUG_MAX_PIXELS, N, C, H, W);
-  HD_CHECK_ARG(aligned16(ws), "hd_augment_u8: ws must be 16-byte aligned");
+  HD_CHECK_ARG(hd_aligned16(ws), "hd_augment_u8: ws must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   uint8_t* tmp = (uint8_t*)ws;
   const size_t acc_words = (size_t)N + (size_t)N * C * 256;
@@ -439,7 +431,7 @@ extern "C" int hd_augment_u8(const uint8_t* x, const float* params, int N, int C
   }
   // 16 bytes per lane: the pointwise passes when every plane starts on a 16-byte boundary (H*W a multiple of 16: the three planes of a
   // pixel are then aligned alike), the sharpness pass when every row does (W a multiple of 16); one byte per lane otherwise
-  const bool base16 = aligned16(x) && aligned16(out);
+  const bool base16 = hd_aligned16(x) && hd_aligned16(out);
   const bool vec_plane = base16 && ((int64_t)H * W) % 16 == 0, vec_row = base16 && (W % 16) == 0;
   if (C == 3) launch_c<3>(vec_plane, vec_row, s, x, params, N, H, W, out, tmp, sums, hist);
   else launch_c<1>(vec_plane, vec_row, s, x, params, N, H, W, out, tmp, sums, hist);

@@ -12,7 +12,7 @@
 // no workspace, no host synchronisation.
 // The source rows are cold HBM by construction (an epoch touches every slot once) and nothing is read twice, so the caches only see a
 // stream; every load and store instruction of a wave covers one contiguous run (kernels below).
-#include "hd_common.h"
+#include "hd_block.h"
 #pragma clang fp contract(off)
 
 namespace {
@@ -105,8 +105,6 @@ void launch(bool vec, hipStream_t s, const uint8_t* arena, int64_t S, const int6
     hipLaunchKernelGGL((batch_gather_f32x4_kernel<MODE>), grid_for(chw / 16, N), block, 0, s, arena, S, idx, chw / 4, static_cast<float*>(out));
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" int hd_batch_gather_u8(const uint8_t* arena, int64_t S, const int64_t* idx, int N, int64_t chw, int mode, void* out, void* stream) {
@@ -120,7 +118,7 @@ extern "C" int hd_batch_gather_u8(const uint8_t* arena, int64_t S, const int64_t
   hipStream_t s = (hipStream_t)stream;
   // the 16-byte path when every slot starts on a 16-byte boundary (C*H*W a multiple of 16 and both bases aligned); one byte per lane
   // otherwise: correct, not tuned
-  const bool vec = chw % 16 == 0 && aligned16(arena) && aligned16(out);
+  const bool vec = chw % 16 == 0 && hd_aligned16(arena) && hd_aligned16(out);
   if (mode == HD_GATHER_U8) launch<HD_GATHER_U8>(vec, s, arena, S, idx, N, chw, out);
   else if (mode == HD_GATHER_F32_DEFAULT) launch<HD_GATHER_F32_DEFAULT>(vec, s, arena, S, idx, N, chw, out);
   else launch<HD_GATHER_F32_IEEE>(vec, s, arena, S, idx, N, chw, out);

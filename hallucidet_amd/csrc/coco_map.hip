@@ -30,7 +30,7 @@
 //   miss rate   (host) mr_i = 1.0 - hit_i / n_gt; lamr = exp(mean(log(max(mr, 1e-10))))
 // One block per (t, k, a) with the chunked block scan of hd_map_accumulate; a counted point raises LDS bin i0 = #{i : ref[i] < fppi}
 // to its tp with an integer max (it qualifies for exactly the rates i >= i0), one thread takes the prefix max over the bins.
-#include "hd_common.h"
+#include "hd_block.h"
 
 namespace {
 
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(64) void map_match_kernel(const double* __restrict_
     const int j = base + lane;
     const bool hit = j < dc && dlabel[(int64_t)n * P + j] == cls;
     const uint64_t bal = __ballot(hit);
-    const int pos = cnt + __popcll(bal & ((1ull << lane) - 1ull));
+    const int pos = cnt + hd_ballot_rank(bal, lane);
     if (hit && pos < DCAP) {
       s_sc[pos] = dscore[(int64_t)n * P + j];
       s_di[pos] = j;
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(64) void map_match_kernel(const double* __restrict_
     const int j = base + lane;
     const bool hit = j < gc && glabel[(int64_t)n * Q + j] == cls;
     const uint64_t bal = __ballot(hit);
-    const int pos = G + __popcll(bal & ((1ull << lane) - 1ull));
+    const int pos = G + hd_ballot_rank(bal, lane);
     if (hit && pos < GCAP) {
       const double* b = gbox + ((int64_t)n * Q + j) * 4;
       s_gb[pos][0] = b[0]; s_gb[pos][1] = b[1]; s_gb[pos][2] = b[2]; s_gb[pos][3] = b[3];
@@ -214,28 +214,6 @@ __global__ __launch_bounds__(64) void map_match_kernel(const double* __restrict_
 constexpr int AB = 256;                 // threads of an accumulate block
 constexpr int AW = AB / 64;
 
-// inclusive block scan of v; returns the block total in *tot
-__device__ __forceinline__ int block_scan(int v, int* sm, int* tot) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int u = __shfl_up(v, d);
-    if (lane >= d) v += u;
-  }
-  if (lane == 63) sm[w] = v;
-  __syncthreads();
-  int off = 0, all = 0;
-#pragma unroll
-  for (int i = 0; i < AW; ++i) {
-    const int s = sm[i];
-    off += i < w ? s : 0;
-    all += s;
-  }
-  __syncthreads();
-  *tot = all;
-  return v + off;
-}
-
 __global__ __launch_bounds__(AB) void map_accumulate_kernel(const int32_t* __restrict__ order, const int32_t* __restrict__ class_off,
                                                             const int32_t* __restrict__ flags, int64_t nk100,
                                                             const int32_t* __restrict__ npig, const int32_t* __restrict__ n_eval, int K,
@@ -282,7 +260,7 @@ __global__ __launch_bounds__(AB) void map_accumulate_kernel(const int32_t* __res
       }
     }
     int tot;
-    const int inc = block_scan(packed, s_scan, &tot);
+    const int inc = hd_block_scan<AW>(packed, s_scan, &tot);
     if (packed) {
       const int tp = run_tp + (inc & 1023), fp = run_fp + ((inc >> 10) & 1023);
       const double tpd = (double)tp, fpd = (double)fp;
@@ -361,7 +339,7 @@ __global__ __launch_bounds__(AB) void mr_accumulate_kernel(const int32_t* __rest
       packed = igb ? 0 : (tpb ? 1 : (1 << 10));        // tp | fp << 10: at most AB of either per chunk
     }
     int tot;
-    const int inc = block_scan(packed, s_scan, &tot);
+    const int inc = hd_block_scan<AW>(packed, s_scan, &tot);
     const int tp = run_tp + (inc & 1023), fp = run_fp + ((inc >> 10) & 1023);
     if (curve && j < hi) {                             // an ignored detection repeats the pair before it
       curve_tp[j] = tp;

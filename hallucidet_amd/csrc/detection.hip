@@ -1,20 +1,13 @@
 // Detection kernels: batched greedy NMS (64-wide bitmask rows: one wavefront lane per
 // mask bit), pairwise IoU, the fused glue kernels (RoIAlign: roi_align.hip).  fp32 box maths with FMA
-// contraction disabled so the keep decisions match the scalar CPU oracle bit for bit.
-#include "hd_common.h"
+// contraction disabled so the keep decisions match the scalar CPU oracle bit for bit.  Box IoU, BoxCoder.encode and the sigmoid are
+// hd_det_math.h's (shared with the loss kernels); wave reductions, the radix select's wave scan, the ordered compaction ranks and the
+// float key are hd_block.h's.
+#include "hd_block.h"
+#include "hd_det_math.h"
 #pragma clang fp contract(off)
 
 namespace {
-
-__device__ __forceinline__ float box_iou_dev(const float* a, const float* b) {
-  float area_a = (a[2] - a[0]) * (a[3] - a[1]);
-  float area_b = (b[2] - b[0]) * (b[3] - b[1]);
-  float xx1 = fmaxf(a[0], b[0]), yy1 = fmaxf(a[1], b[1]);
-  float xx2 = fminf(a[2], b[2]), yy2 = fminf(a[3], b[3]);
-  float w = fmaxf(0.f, xx2 - xx1), h = fmaxf(0.f, yy2 - yy1);
-  float inter = w * h;
-  return inter / (area_a + area_b - inter);
-}
 
 // grid (colblk, rowblk, B), block 64.  mask[b][i][colblk] bit j set <=> IoU(box i, box col*64+j) > thr, j-index > i
 __global__ void nms_mask_kernel(const float* __restrict__ boxes, const int* __restrict__ counts, int nmax, float thr,
@@ -158,11 +151,7 @@ __global__ __launch_bounds__(256) void nms_prepare_kernel(const float* __restric
       m = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
       ++cnt;
     }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    m = fmaxf(m, __shfl_xor(m, d));
-    cnt += __shfl_xor(cnt, d);
-  }
+  hd_wave_reduce2(m, HdMax(), cnt, HdSum());
   if ((tid & 63) == 0) {
     s_max[tid >> 6] = m;
     s_cnt[tid >> 6] = cnt;
@@ -210,11 +199,7 @@ __global__ __launch_bounds__(256) void nms_seg_prepare_kernel(const float* __res
       m = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
       ++cnt;
     }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    m = fmaxf(m, __shfl_xor(m, d));
-    cnt += __shfl_xor(cnt, d);
-  }
+  hd_wave_reduce2(m, HdMax(), cnt, HdSum());
   if (lane == 0) {
     s_max[wave] = m;
     s_cnt[wave] = cnt;
@@ -232,21 +217,17 @@ __global__ __launch_bounds__(256) void nms_seg_prepare_kernel(const float* __res
     for (int c0 = lo; c0 < hi; c0 += 256) {
       const int i = c0 + tid;
       const bool v = i < hi && vb[i];
-      const uint64_t bal = __ballot(v);
-      const int before = __popcll(bal & ((1ull << lane) - 1ull));
       __syncthreads();                       // s_wsum of the previous round has been read
-      if (lane == 0) s_wsum[wave] = __popcll(bal);
-      __syncthreads();
-      int wbase = 0;
-      for (int w = 0; w < wave; ++w) wbase += s_wsum[w];
+      int all;
+      const int rank = hd_block_rank<4>(v, s_wsum, &all);
       if (v) {
-        const int r = base + wbase + before;
+        const int r = base + rank;
         float4 bx = *reinterpret_cast<const float4*>(bb + (size_t)i * 4);
         bx.x += off; bx.y += off; bx.z += off; bx.w += off;
         *reinterpret_cast<float4*>(so + (size_t)r * 4) = bx;
         oo[r] = i;
       }
-      base += s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3];
+      base += all;
     }
     if (tid == 0) counts[b * sg.L + l] = base;
   }
@@ -343,12 +324,7 @@ __device__ __forceinline__ void radix_find_digit(const int* hist, int remaining,
     h[j] = hist[DESC ? 255 - (4 * l + j) : 4 * l + j];
     tot += h[j];
   }
-  int incl = tot;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(incl, d);
-    if (l >= d) incl += t;
-  }
+  const int incl = hd_wave_scan(tot, l);
   const int excl = incl - tot;
   const bool hit = excl < remaining && remaining <= incl;
   const bool fallback = l == 63 && incl < remaining;          // cannot happen for consistent inputs; keeps the state defined
@@ -373,8 +349,8 @@ __device__ __forceinline__ void radix_find_digit(const int* hist, int remaining,
 __device__ __forceinline__ uint32_t order_key(float f) {
   if (f != f) return 0xFFFFFFFFu;                           // every NaN, whatever its sign and payload: the one largest key (above +inf =
                                                             // 0xFF800000) -- torch.sort lists the NaNs first, in index order
-  uint32_t u = __float_as_uint(f == 0.f ? 0.f : f);        // -0.0 and +0.0 compare equal (ties go by index), as in torch.sort
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);        // larger float <=> larger key
+  return hd_float_key(f == 0.f ? 0.f : f);                  // -0.0 and +0.0 compare equal (ties go by index), as in torch.sort;
+                                                            // larger float <=> larger key
 }
 
 struct TopkSegs {
@@ -425,13 +401,13 @@ __global__ __launch_bounds__(1024) void topk_select_kernel(const float* __restri
       const uint32_t u = i < n ? order_key(row[i]) : 0u;
       const bool gt = i < n && u > T, eq = i < n && u == T;
       const uint64_t bg = __ballot(gt), be = __ballot(eq);
-      const uint64_t below = (1ull << lane) - 1ull;
       if (lane == 0) {
         s_wave_g[wave] = __popcll(bg);
         s_wave_e[wave] = __popcll(be);
       }
       __syncthreads();
-      int g_before = base_g + __popcll(bg & below), e_before = base_e + __popcll(be & below);
+      // (two flags share one barrier here: hd_block_rank's counting, written out for the pair)
+      int g_before = base_g + hd_ballot_rank(bg, lane), e_before = base_e + hd_ballot_rank(be, lane);
       int tot_g = 0, tot_e = 0;
 #pragma unroll
       for (int w = 0; w < 16; ++w) {
@@ -506,8 +482,7 @@ __global__ void rpn_decode_filter_kernel(const float* __restrict__ deltas, const
   const int n = j / K;
   const int64_t a = top[j];
   const float4 o = decode_clip_dev(deltas + ((size_t)n * A + a) * 4, anchors + (size_t)a * 4, 1.f, 1.f, 1.f, 1.f, xclip, img_h, img_w);
-  const float x = obj[(size_t)n * A + a];
-  const float p = 1.f / (1.f + expf(-x));
+  const float p = hd_sigmoid(obj[(size_t)n * A + a]);
   *reinterpret_cast<float4*>(boxes + (size_t)j * 4) = o;
   prob[j] = p;
   valid[j] = ((o.z - o.x) >= min_size) && ((o.w - o.y) >= min_size) && (p >= score_thresh);
@@ -584,16 +559,7 @@ __global__ void roi_samples_finish_kernel(const int64_t* __restrict__ sel, int R
   rois[(size_t)r * 5 + 3] = b.z;
   rois[(size_t)r * 5 + 4] = b.w;
   labels[r] = lab[s];
-  const float ew = b.z - b.x, eh = b.w - b.y;
-  const float ecx = b.x + 0.5f * ew, ecy = b.y + 0.5f * eh;
-  const float gw = rg.z - rg.x, gh = rg.w - rg.y;
-  const float gcx = rg.x + 0.5f * gw, gcy = rg.y + 0.5f * gh;
-  float4 t;
-  t.x = wx * (gcx - ecx) / ew;
-  t.y = wy * (gcy - ecy) / eh;
-  t.z = ww * logf(gw / ew);
-  t.w = wh * logf(gh / eh);
-  *reinterpret_cast<float4*>(reg_t + (size_t)r * 4) = t;
+  *reinterpret_cast<float4*>(reg_t + (size_t)r * 4) = encode_box(rg, b, wx, wy, ww, wh);
 }
 
 // Fixed-size form of the above, compaction included: one block per image scans its T candidates (selected = pos | neg), the r-th
@@ -618,7 +584,7 @@ __global__ __launch_bounds__(256) void roi_samples_padded_kernel(const uint8_t* 
                                                                  float* __restrict__ reg_t, int64_t* __restrict__ counts) {
   __shared__ int wsum[4];
   __shared__ int carry;
-  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int n = blockIdx.x, tid = threadIdx.x;
   bool has_gt = false;
   for (int g = 0; g < G; ++g) has_gt = has_gt || gvalid[(size_t)n * G + g];
   if (tid == 0) carry = 0;
@@ -627,27 +593,18 @@ __global__ __launch_bounds__(256) void roi_samples_padded_kernel(const uint8_t* 
     const int t = t0 + tid;
     const size_t s = (size_t)n * T + t;
     const bool on = t < T && (pos_sel[s] | neg_sel[s]);
-    const unsigned long long bal = __ballot(on);
-    const int in_wave = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[w] = __popcll(bal);
-    __syncthreads();
-    int before = carry;
-    for (int k = 0; k < w; ++k) before += wsum[k];
-    const int r = before + in_wave;
+    int all;
+    const int rank = hd_block_rank<4>(on, wsum, &all);
+    const int r = carry + rank;
     if (on && r < S) {
       const float4 b = *reinterpret_cast<const float4*>(comb + s * 4);
       const int64_t m = matched[s];
       float4 rg = make_float4(0.f, 0.f, 0.f, 0.f);
       if (has_gt) rg = *reinterpret_cast<const float4*>(gt + ((size_t)n * G + (m > 0 ? m : 0)) * 4);
-      const float ew = b.z - b.x, eh = b.w - b.y;
-      const float ecx = b.x + 0.5f * ew, ecy = b.y + 0.5f * eh;
-      const float gw = rg.z - rg.x, gh = rg.w - rg.y;
-      const float gcx = rg.x + 0.5f * gw, gcy = rg.y + 0.5f * gh;
-      roi_row_write(n * S + r, n, b, lab[s], make_float4(wx * (gcx - ecx) / ew, wy * (gcy - ecy) / eh, ww * logf(gw / ew), wh * logf(gh / eh)), rois,
-                    labels, reg_t);
+      roi_row_write(n * S + r, n, b, lab[s], encode_box(rg, b, wx, wy, ww, wh), rois, labels, reg_t);
     }
     __syncthreads();
-    if (tid == 0) carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    if (tid == 0) carry += all;
     __syncthreads();
   }
   const int cnt = carry < S ? carry : S;
@@ -680,7 +637,7 @@ __device__ __forceinline__ void select_smallest_marked(const int32_t* __restrict
                                                        int k, int population, uint8_t* __restrict__ out, int* hist, uint32_t* s_prefix,
                                                        int* s_remaining, int* s_wave_l, int* s_wave_e, const uint32_t* lds_keys = nullptr,
                                                        const uint8_t* lds_cls = nullptr) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   auto member = [&](int i) {
     if (lds_cls) return lds_cls[i] == (want_pos ? 1 : 0);
     const int64_t l = labels[i];
@@ -721,16 +678,8 @@ __device__ __forceinline__ void select_smallest_marked(const int32_t* __restrict
     const bool mem = i < A && member(i);
     const uint32_t u = mem ? key_of(i) : 0xFFFFFFFFu;
     const bool lt = mem && u < T, eq = mem && u == T;
-    const uint64_t be = __ballot(eq);
-    if (lane == 0) s_wave_e[wave] = __popcll(be);
-    __syncthreads();
-    int e_before = base_e + __popcll(be & ((1ull << lane) - 1ull));
-    int tot_e = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-      if (w < wave) e_before += s_wave_e[w];
-      tot_e += s_wave_e[w];
-    }
+    int tot_e;
+    const int e_before = base_e + hd_block_rank<16>(eq, s_wave_e, &tot_e);
     if (i < A) out[i] = (lt || (eq && e_before < remaining)) ? 1 : 0;
     base_e += tot_e;
     __syncthreads();
@@ -763,11 +712,7 @@ __global__ __launch_bounds__(1024) void sample_pos_neg_kernel(const int64_t* __r
       lc[i] = l >= 1 ? 1 : (l == 0 ? 0 : 2);
     }
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    p += __shfl_xor(p, d);
-    q += __shfl_xor(q, d);
-  }
+  hd_wave_reduce2(p, HdSum(), q, HdSum());
   if ((tid & 63) == 0) {
     atomicAdd(&s_P, p);
     atomicAdd(&s_N, q);
@@ -806,10 +751,7 @@ __global__ __launch_bounds__(1024) void match_best_kernel(const float* __restric
     const float* bb = boxes + (size_t)n * boxes_stride;
     for (int a = threadIdx.x; a < A; a += 1024) m = fmaxf(m, box_iou_dev(g4, bb + (size_t)a * 4));
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
+  hd_block_put(hd_wave_reduce(m, HdMax()), red);
   if (threadIdx.x == 0) {
     float r = red[0];
 #pragma unroll
@@ -863,16 +805,8 @@ __global__ __launch_bounds__(256) void match_assign_kernel(const float* __restri
   }
   if (want_reg) {
     const float* r = s_gt + (m > 0 ? (int)m : 0) * 4;         // matched.clamp(min=0)
-    const float ew = b4[2] - b4[0], eh = b4[3] - b4[1];
-    const float ecx = b4[0] + 0.5f * ew, ecy = b4[1] + 0.5f * eh;
-    const float gw = r[2] - r[0], gh = r[3] - r[1];
-    const float gcx = r[0] + 0.5f * gw, gcy = r[1] + 0.5f * gh;
-    float4 t;
-    t.x = wx * (gcx - ecx) / ew;
-    t.y = wy * (gcy - ecy) / eh;
-    t.z = ww * logf(gw / ew);
-    t.w = wh * logf(gh / eh);
-    *reinterpret_cast<float4*>(reg_t + o * 4) = t;
+    *reinterpret_cast<float4*>(reg_t + o * 4) =
+        encode_box(make_float4(r[0], r[1], r[2], r[3]), make_float4(b4[0], b4[1], b4[2], b4[3]), wx, wy, ww, wh);
   }
 }
 

@@ -3,7 +3,8 @@
 // center-sampling target assignment of FCOS.compute_loss, and the three losses of FCOSHead.compute_loss (sigmoid focal,
 // generalized IoU on decoded boxes, centre-ness BCE) as one forward and one backward launch.
 // All of it is HBM / latency bound work on small tensors (5 pyramid levels of a 300 x 300 image: 1 939 locations).
-#include "hd_common.h"
+#include "hd_block.h"
+#include "hd_det_math.h"
 
 namespace {
 
@@ -230,40 +231,6 @@ __global__ void fcos_match_kernel(const float* __restrict__ anchors, const float
 constexpr int LB = 256;
 constexpr int FB = 64;      // partial-sum blocks
 
-struct FocalT {
-  float ce, p;
-};
-__device__ __forceinline__ FocalT focal_terms(float x) {
-  FocalT r;
-  r.p = 1.f / (1.f + expf(-x));
-  const float m = fmaxf(-x, 0.f);
-  r.ce = m + logf(expf(-m) + expf(-x - m));
-  return r;
-}
-__device__ __forceinline__ float focal_value(float x, bool t, float alpha, float gamma) {
-  const FocalT f = focal_terms(x);
-  const float ce = t ? f.ce : x + f.ce;
-  const float pt = t ? f.p : 1.f - f.p;
-  const float w = gamma == 2.f ? (1.f - pt) * (1.f - pt) : powf(1.f - pt, gamma);
-  float l = ce * w;
-  if (alpha >= 0.f) l *= t ? alpha : 1.f - alpha;
-  return l;
-}
-__device__ __forceinline__ float focal_grad(float x, bool t, float alpha, float gamma) {
-  const FocalT f = focal_terms(x);
-  const float p = f.p, q = 1.f - f.p;
-  float g;
-  if (t) {
-    const float w = gamma == 2.f ? q * q : powf(q, gamma);
-    g = w * (-gamma * p * f.ce - q);
-  } else {
-    const float w = gamma == 2.f ? p * p : powf(p, gamma);
-    g = w * (p + gamma * q * (x + f.ce));
-  }
-  if (alpha >= 0.f) g *= t ? alpha : 1.f - alpha;
-  return g;
-}
-
 struct Giou {
   float loss;
   float d[4];      // d loss / d (x1, y1, x2, y2) of the predicted box
@@ -309,21 +276,6 @@ __device__ __forceinline__ float ctr_target(float cx, float cy, float4 g) {
   return sqrtf((fminf(l, r) / fmaxf(l, r)) * (fminf(t, b) / fmaxf(t, b)));
 }
 
-__device__ __forceinline__ void block_sum4(float (&v)[4], float* sm) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v[k] += __shfl_xor(v[k], d);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) sm[w * 4 + k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = (sm[k] + sm[4 + k]) + (sm[8 + k] + sm[12 + k]);
-}
-
 // part [FB][4] = (focal sum, giou sum, centre-ness sum, #foreground) over the block's (image, location) range
 __global__ __launch_bounds__(LB) void fcos_loss_fwd_kernel(const float* __restrict__ logits, const float* __restrict__ breg, const float* __restrict__ ctr,
                                                            const int64_t* __restrict__ matched, const float* __restrict__ gt,
@@ -346,12 +298,16 @@ __global__ __launch_bounds__(LB) void fcos_loss_fwd_kernel(const float* __restri
       const float cx = 0.5f * (an.x + an.z), cy = 0.5f * (an.y + an.w), w = an.z - an.x, h = an.w - an.y;
       acc[1] += giou_terms(cx - d.x * w, cy - d.y * h, cx + d.z * w, cy + d.w * h, g, false).loss;
       const float t = ctr_target(cx, cy, g), x = ctr[i];
-      const float mm = fmaxf(-x, 0.f);
-      acc[2] += (1.f - t) * x + mm + logf(expf(-mm) + expf(-x - mm));
+      acc[2] += hd_bce_logits(x, t);
       acc[3] += 1.f;
     }
   }
-  block_sum4(acc, sm);
+  // four block sums, one wave reduction after the other, the wave partials folded pairwise: (w0 + w1) + (w2 + w3)
+#pragma unroll
+  for (int k = 0; k < 4; ++k) acc[k] = hd_wave_reduce(acc[k], HdSum());
+  hd_block_put(acc, sm);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) acc[k] = (sm[k] + sm[4 + k]) + (sm[8 + k] + sm[12 + k]);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) part[blockIdx.x * 4 + k] = acc[k];
@@ -396,7 +352,7 @@ __global__ __launch_bounds__(LB) void fcos_loss_bwd_kernel(const float* __restri
       const Giou q = giou_terms(cx - d.x * w, cy - d.y * h, cx + d.z * w, cy + d.w * h, g, true);
       o = make_float4(-w * q.d[0] * gr, -h * q.d[1] * gr, w * q.d[2] * gr, h * q.d[3] * gr);
       const float t = ctr_target(cx, cy, g), x = ctr[i];
-      dc = (1.f / (1.f + expf(-x)) - t) * gt_;
+      dc = (hd_sigmoid(x) - t) * gt_;
     }
     *reinterpret_cast<float4*>(d_breg + i * 4) = o;
     d_ctr[i] = dc;

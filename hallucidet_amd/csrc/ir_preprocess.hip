@@ -15,7 +15,7 @@
 // The accumulators are cleared by one launch in front of the first pass.  Histograms are 32-bit integer counts (registers -> LDS ->
 // one global atomic per block and bin): the result does not depend on the order of arrival.  Every fp32 step below is one IEEE
 // operation: no contraction, true divisions.
-#include "hd_common.h"
+#include "hd_block.h"
 #pragma clang fp contract(off)
 
 namespace {
@@ -41,14 +41,6 @@ constexpr float Q_HI = (float)(1.0 - 0.003);
 constexpr float G_A = 0x1.e975d4p-3f, G_B = 0x1.0b4518p-1f;
 constexpr float W_AA = G_A * G_A, W_AB = G_A * G_B, W_BB = G_B * G_B;
 
-__device__ __forceinline__ uint32_t float_key(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_float(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
-
 __device__ __forceinline__ float invert_n(float v, int n) {
   for (int i = 0; i < n; ++i) v = 1.0f - v;
   return v;
@@ -59,26 +51,6 @@ __device__ __forceinline__ int quantise(float v) {
   const float s = v * 255.0f;
   const int u = (int)s;
   return u < 0 ? 0 : (u > 255 ? 255 : u);
-}
-
-template <int V>
-__device__ __forceinline__ void ldv(const float* p, float (&v)[V]) {
-  if constexpr (V == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = *p;
-  }
-}
-template <int V>
-__device__ __forceinline__ void stv(float* p, const float (&v)[V]) {
-  if constexpr (V == 4) {
-    f32x4 t;
-    t.x = v[0]; t.y = v[1]; t.z = v[2]; t.w = v[3];
-    *reinterpret_cast<f32x4*>(p) = t;
-  } else {
-    *p = v[0];
-  }
 }
 
 // run-length front of an LDS histogram: a thread's consecutive hits of one bin cost one atomic (8-bit images and the exponent byte
@@ -125,11 +97,11 @@ __global__ __launch_bounds__(TB) void irp_hist_kernel(const float* __restrict__ 
     Run run;
     for (int g = blockIdx.x * TB + threadIdx.x; g < groups; g += gridDim.x * TB) {
       float v[V];
-      ldv<V>(pl + (size_t)g * V, v);
+      hd_ldv<V>(pl + (size_t)g * V, v);
 #pragma unroll
       for (int k = 0; k < V; ++k) {
         const float t = invert_n(v[k], npre);
-        run.add(sh, level < 0 ? quantise(t) : (int)(float_key(t) >> 24));
+        run.add(sh, level < 0 ? quantise(t) : (int)(hd_float_key(t) >> 24));
       }
     }
     run.flush(sh);
@@ -139,10 +111,10 @@ __global__ __launch_bounds__(TB) void irp_hist_kernel(const float* __restrict__ 
     Run r0, r1, r2, r3;
     for (int g = blockIdx.x * TB + threadIdx.x; g < groups; g += gridDim.x * TB) {
       float v[V];
-      ldv<V>(pl + (size_t)g * V, v);
+      hd_ldv<V>(pl + (size_t)g * V, v);
 #pragma unroll
       for (int k = 0; k < V; ++k) {
-        const uint32_t key = float_key(invert_n(v[k], npre));
+        const uint32_t key = hd_float_key(invert_n(v[k], npre));
         const uint32_t pfx = key >> (shift + 8);
         const int d = (int)((key >> shift) & 255u);
         if (pfx == p0) r0.add(sh, d);
@@ -188,12 +160,7 @@ __global__ __launch_bounds__(TB) void irp_resolve_kernel(uint32_t* __restrict__ 
   const uint32_t* h = level == 0 ? a + A_HIST0 : a + A_HISTL + ((level - 1) * 4 + t) * 256;
   const uint32_t b0 = h[4 * lane], b1 = h[4 * lane + 1], b2 = h[4 * lane + 2], b3 = h[4 * lane + 3];
   const uint32_t s = b0 + b1 + b2 + b3;
-  uint32_t incl = s;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(incl, d);
-    if (lane >= d) incl += o;
-  }
+  const uint32_t incl = hd_wave_scan(s, lane);
   uint32_t e = incl - s;
   if (rem >= e && rem < incl) {          // one lane of the wave
     int d = 0;
@@ -209,7 +176,7 @@ __global__ __launch_bounds__(TB) void irp_resolve_kernel(uint32_t* __restrict__ 
     const uint32_t np = (prefix << 8) | (uint32_t)(4 * lane + d);
     a[A_PREFIX + t] = np;
     a[A_REM + t] = rem - e;
-    if (level == 3) vals[t] = key_float(np);
+    if (level == 3) vals[t] = hd_key_float(np);
   }
   if (level != 3) return;
   __syncthreads();
@@ -263,15 +230,8 @@ __global__ __launch_bounds__(TB) void irp_point_kernel(const float* __restrict__
     // lut[i] = min((sum of the bins below i + step // 2) // step, 255)
     const int i = threadIdx.x, w = i >> 6, lane = i & 63;
     const uint32_t h = acc[(size_t)plane * A_WORDS + A_HIST0 + i];
-    uint32_t incl = h;
-    int last = h ? i : -1;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t o = __shfl_up(incl, d);
-      if (lane >= d) incl += o;
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) last = max(last, __shfl_xor(last, d));
+    const uint32_t incl = hd_wave_scan(h, lane);
+    int last = hd_wave_reduce(h ? i : -1, HdMax());
     if (lane == 63) wsum[w] = incl;
     if (lane == 0) wlast[w] = last;
     __syncthreads();
@@ -293,7 +253,7 @@ __global__ __launch_bounds__(TB) void irp_point_kernel(const float* __restrict__
   const int groups = P / V;
   for (int g = blockIdx.x * TB + threadIdx.x; g < groups; g += gridDim.x * TB) {
     float v[V];
-    ldv<V>(pi + (size_t)g * V, v);
+    hd_ldv<V>(pi + (size_t)g * V, v);
 #pragma unroll
     for (int k = 0; k < V; ++k) {
       float t = invert_n(v[k], npre);
@@ -306,7 +266,7 @@ __global__ __launch_bounds__(TB) void irp_point_kernel(const float* __restrict__
       }
       v[k] = invert_n(t, npost);
     }
-    stv<V>(po + (size_t)g * V, v);
+    hd_stv<V>(po + (size_t)g * V, v);
   }
 }
 
@@ -326,7 +286,7 @@ __global__ __launch_bounds__(TB) void irp_blur_kernel(const float* __restrict__ 
   for (int g = blockIdx.x * TB + threadIdx.x; g < groups; g += gridDim.x * TB) {
     const int p0 = g * V;
     float mid[V], res[V];
-    ldv<V>(pl + p0, mid);
+    hd_ldv<V>(pl + p0, mid);
 #pragma unroll
     for (int k = 0; k < V; ++k) mid[k] = invert_n(mid[k], npre);
     if (active) {
@@ -337,8 +297,8 @@ __global__ __launch_bounds__(TB) void irp_blur_kernel(const float* __restrict__ 
       const float* rm = pl + (size_t)y * W;
       const float* rd = pl + (size_t)yp * W;
       float up[V], dn[V];
-      ldv<V>(ru + x0, up);
-      ldv<V>(rd + x0, dn);
+      hd_ldv<V>(ru + x0, up);
+      hd_ldv<V>(rd + x0, dn);
       float l3[3] = {ru[xl], rm[xl], rd[xl]}, r3[3] = {ru[xr], rm[xr], rd[xr]};
 #pragma unroll
       for (int k = 0; k < V; ++k) {
@@ -371,7 +331,7 @@ __global__ __launch_bounds__(TB) void irp_blur_kernel(const float* __restrict__ 
 #pragma unroll
       for (int k = 0; k < V; ++k) res[k] = invert_n(mid[k], npost);
     }
-    stv<V>(po + p0, res);
+    hd_stv<V>(po + p0, res);
   }
 }
 
@@ -380,7 +340,6 @@ struct Pass {
 };
 
 inline size_t round256(size_t v) { return (v + 255) & ~(size_t)255; }
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool shape_ok(int N, int C, int H, int W, int n_stage) {
   return N > 0 && (C == 1 || C == 3) && (int64_t)N * C <= 65535 && H >= 2 && W >= 2 && (int64_t)H * W <= HD_IRP_MAX_PIXELS && n_stage >= 1 &&
          n_stage <= HD_IRP_MAX_STAGES;
@@ -410,7 +369,7 @@ extern "C" int hd_ir_preprocess(const float* x, int N, int C, int H, int W, cons
   HD_CHECK_ARG(x && stages && out && ws, "hd_ir_preprocess: null pointer (x, stages, out and ws are required)");
   HD_CHECK_ARG(shape_ok(N, C, H, W, n_stage), "hd_ir_preprocess: " SHAPE_MSG, HD_IRP_MAX_PIXELS, HD_IRP_MAX_STAGES, N, C, H, W, n_stage);
   HD_CHECK_ARG(x != out, "hd_ir_preprocess: out must not be x");
-  HD_CHECK_ARG(aligned16(ws), "hd_ir_preprocess: ws must be 16-byte aligned");
+  HD_CHECK_ARG(hd_aligned16(ws), "hd_ir_preprocess: ws must be 16-byte aligned");
   // stage list -> passes: inverts wait (a count per channel, 4 bits each) for the next stage that reads or, at the end, the last that wrote
   Pass passes[HD_IRP_MAX_STAGES];
   int n_pass = 0, pending = 0;
@@ -442,7 +401,7 @@ extern "C" int hd_ir_preprocess(const float* x, int N, int C, int H, int W, cons
   }
   // 16 bytes per lane: the passes that walk the flat plane when every plane starts on a 16-byte boundary (H*W a multiple of 4), the
   // stencil when every row does (W a multiple of 4); one float per lane otherwise
-  const bool base16 = aligned16(x) && aligned16(out);
+  const bool base16 = hd_aligned16(x) && hd_aligned16(out);
   const bool vec_plane = base16 && (P % 4) == 0, vec_row = base16 && (W % 4) == 0;
   const dim3 block(TB);
   const dim3 gh = grid_for(P, vec_plane ? 4 : 1, planes, MAXBX_HIST), gp = grid_for(P, vec_plane ? 4 : 1, planes, MAXBX);

@@ -1,37 +1,16 @@
 // Detector losses as single launches, forward and backward (torchvision RegionProposalNetwork.compute_loss and
 // roi_heads.fastrcnn_loss [EXT], reached from src/utils/eval_forward_fasterrcnn.py:93,141 in the reference).
 // The per-op torch form is ~25 elementwise / reduction launches forward and ~25 backward over [N*A] / [R] tensors.
-// Per element the arithmetic is ATen's: BCE-with-logits = (1-t)*x + m + log(exp(-m) + exp(-x-m)), m = max(-x, 0);
-// smooth-L1(beta) = 0.5*d*d/beta below beta, |d| - 0.5*beta above; cross entropy through a max-shifted log-softmax.
-// Sums are two-stage (fixed block partials, then one block in index order): deterministic.
-#include "hd_common.h"
+// Per element the arithmetic is ATen's: BCE-with-logits, smooth-L1(beta), the focal terms and BoxCoder.encode are hd_det_math.h's
+// (shared with fcos.hip and detection.hip); cross entropy through a max-shifted log-softmax is here.
+// Sums are two-stage (fixed block partials through hd_block.h's hd_block_sum2, then one block in index order): deterministic.
+#include "hd_block.h"
+#include "hd_det_math.h"
 
 namespace {
 
 constexpr int LB = 256;       // threads per block
 constexpr int NPART = 256;    // partial-sum blocks
-
-__device__ __forceinline__ float smooth_l1(float d, float beta) {
-  const float z = fabsf(d);
-  return z < beta ? 0.5f * z * z / beta : z - 0.5f * beta;
-}
-__device__ __forceinline__ float smooth_l1_grad(float d, float beta) { return d < -beta ? -1.f : (d > beta ? 1.f : d / beta); }
-
-__device__ __forceinline__ void block_sum2(float& a, float& b, float* sm) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    a += __shfl_xor(a, d);
-    b += __shfl_xor(b, d);
-  }
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    sm[w * 2] = a;
-    sm[w * 2 + 1] = b;
-  }
-  __syncthreads();
-  a = sm[0] + sm[2] + sm[4] + sm[6];
-  b = sm[1] + sm[3] + sm[5] + sm[7];
-}
 
 __global__ __launch_bounds__(LB) void rpn_loss_fwd_kernel(const float* __restrict__ obj, const float* __restrict__ deltas,
                                                           const float* __restrict__ labels, const float* __restrict__ reg_t,
@@ -41,9 +20,7 @@ __global__ __launch_bounds__(LB) void rpn_loss_fwd_kernel(const float* __restric
   float so = 0.f, sb = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * LB + threadIdx.x; i < T; i += (int64_t)gridDim.x * LB) {
     if (samp[i]) {
-      const float x = obj[i], t = labels[i];
-      const float m = fmaxf(-x, 0.f);
-      so += (1.f - t) * x + m + logf(expf(-m) + expf(-x - m));
+      so += hd_bce_logits(obj[i], labels[i]);
     }
     if (pos[i]) {
       const float4 d = *reinterpret_cast<const float4*>(deltas + i * 4);
@@ -51,7 +28,7 @@ __global__ __launch_bounds__(LB) void rpn_loss_fwd_kernel(const float* __restric
       sb += ((smooth_l1(d.x - r.x, beta) + smooth_l1(d.y - r.y, beta)) + smooth_l1(d.z - r.z, beta)) + smooth_l1(d.w - r.w, beta);
     }
   }
-  block_sum2(so, sb, sm);
+  hd_block_sum2<LB / 64>(so, sb, sm);
   if (threadIdx.x == 0) {
     part[blockIdx.x * 2] = so;
     part[blockIdx.x * 2 + 1] = sb;
@@ -67,7 +44,7 @@ __global__ __launch_bounds__(LB) void loss_finish_kernel(const float* __restrict
     a += part[i * 2];
     b += part[i * 2 + 1];
   }
-  block_sum2(a, b, sm);
+  hd_block_sum2<LB / 64>(a, b, sm);
   if (threadIdx.x == 0) {
     float dn = denom_dev ? (float)*denom_dev : denom_host;
     dn = dn < 1.f ? 1.f : dn;
@@ -88,8 +65,7 @@ __global__ __launch_bounds__(LB) void rpn_loss_bwd_kernel(const float* __restric
   for (int64_t i = (int64_t)blockIdx.x * LB + threadIdx.x; i < T; i += (int64_t)gridDim.x * LB) {
     float v = 0.f;
     if (samp[i]) {
-      const float x = obj[i];
-      v = (1.f / (1.f + expf(-x)) - labels[i]) * go;
+      v = (hd_sigmoid(obj[i]) - labels[i]) * go;
     }
     d_obj[i] = v;
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -126,7 +102,7 @@ __global__ __launch_bounds__(LB) void frcnn_loss_fwd_kernel(const float* __restr
       sb += ((smooth_l1(d.x - t.x, beta) + smooth_l1(d.y - t.y, beta)) + smooth_l1(d.z - t.z, beta)) + smooth_l1(d.w - t.w, beta);
     }
   }
-  block_sum2(sc, sb, sm);
+  hd_block_sum2<LB / 64>(sc, sb, sm);
   if (threadIdx.x == 0) {
     part[blockIdx.x * 2] = sc;
     part[blockIdx.x * 2 + 1] = sb;
@@ -173,45 +149,6 @@ __global__ __launch_bounds__(LB) void frcnn_loss_bwd_kernel(const float* __restr
 //   focal(x, t) = alpha_t * bce(x, t) * (1 - p_t)^gamma            (ATen's BCE-with-logits form, p = sigmoid(x))
 //   losses: sum over the image / max(1, #foreground), then the mean over images.
 // Sums are fixed-order block partials per image: deterministic.
-struct FocalT {
-  float ce, p;
-};
-__device__ __forceinline__ FocalT focal_terms(float x) {
-  FocalT r;
-  r.p = 1.f / (1.f + expf(-x));
-  const float m = fmaxf(-x, 0.f);
-  r.ce = m + logf(expf(-m) + expf(-x - m));     // bce(x, t) = (1 - t) * x + this
-  return r;
-}
-__device__ __forceinline__ float focal_value(float x, bool t, float alpha, float gamma) {
-  const FocalT f = focal_terms(x);
-  const float ce = t ? f.ce : x + f.ce;
-  const float pt = t ? f.p : 1.f - f.p;
-  const float w = gamma == 2.f ? (1.f - pt) * (1.f - pt) : powf(1.f - pt, gamma);
-  float l = ce * w;
-  if (alpha >= 0.f) l *= t ? alpha : 1.f - alpha;
-  return l;
-}
-__device__ __forceinline__ float focal_grad(float x, bool t, float alpha, float gamma) {
-  const FocalT f = focal_terms(x);
-  const float p = f.p, q = 1.f - f.p;
-  float g;
-  if (t) {
-    const float w = gamma == 2.f ? q * q : powf(q, gamma);
-    g = w * (-gamma * p * f.ce - q);
-  } else {
-    const float w = gamma == 2.f ? p * p : powf(p, gamma);
-    g = w * (p + gamma * q * (x + f.ce));
-  }
-  if (alpha >= 0.f) g *= t ? alpha : 1.f - alpha;
-  return g;
-}
-__device__ __forceinline__ float4 encode_box(float4 g, float4 a, float wx, float wy, float ww, float wh) {
-  const float ew = a.z - a.x, eh = a.w - a.y, ecx = a.x + 0.5f * ew, ecy = a.y + 0.5f * eh;
-  const float gw = g.z - g.x, gh = g.w - g.y, gcx = g.x + 0.5f * gw, gcy = g.y + 0.5f * gh;
-  return make_float4(wx * (gcx - ecx) / ew, wy * (gcy - ecy) / eh, ww * logf(gw / ew), wh * logf(gh / eh));
-}
-
 constexpr int RB = 32;     // blocks per image
 
 // part [B][RB][3] = (focal sum, smooth-L1 sum, #foreground) of the block's anchor range
@@ -238,10 +175,9 @@ __global__ __launch_bounds__(LB) void retina_loss_fwd_kernel(const float* __rest
       sb += ((smooth_l1(d.x - t.x, beta) + smooth_l1(d.y - t.y, beta)) + smooth_l1(d.z - t.z, beta)) + smooth_l1(d.w - t.w, beta);
     }
   }
-  block_sum2(sc, sb, sm);
-  __syncthreads();
-  float dummy = 0.f;
-  block_sum2(nf, dummy, sm);
+  hd_block_sum2<LB / 64>(sc, sb, sm);
+  __syncthreads();                       // the first pass's partials have been read: sm serves the third value
+  nf = hd_block_reduce<LB / 64>(nf, HdSum(), sm);
   if (threadIdx.x == 0) {
     float* o = part + ((size_t)b * RB + blockIdx.x) * 3;
     o[0] = sc;

@@ -9,7 +9,7 @@
 //                            row (ground truths, barrier, detections), then stores the row in 16-byte pieces (single bytes only up to
 //                            the first and after the last 16-byte boundary).  Padding rows are stored as zeros directly.
 // Every output byte has one writer and the painting order is fixed by barriers: the same bytes from run to run.
-#include "hd_common.h"
+#include "hd_block.h"
 #include <math.h>
 
 namespace {
@@ -22,23 +22,6 @@ constexpr int LDS_DATA_MAX = 40 * 1024;   // most bytes of one unit (9 cells at 
 constexpr int UNIT_MIN_BYTES = 4096;      // a cell group is not split below this many bytes per unit
 constexpr int MAX_BLOCKS = 2048;
 constexpr int MAX_IMAGES = 16384;         // 3 * N is a grid dimension of the min/max pass
-
-// order-preserving map float -> uint32 (and back): integer min / max of the keys = float min / max
-__device__ __forceinline__ uint32_t f2key(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-template <int V>
-__device__ __forceinline__ void ldv(const float* p, float (&v)[V]) {
-  if constexpr (V == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = *p;
-  }
-}
 
 // grid (B, N * PC): block b of plane (n, c) reduces floats [b * chunk, min((b + 1) * chunk, HW)) of it; chunk % 4 == 0
 template <int V>
@@ -54,24 +37,16 @@ __global__ __launch_bounds__(LB) void media_minmax_kernel(const float* __restric
 #pragma unroll 4
   for (int64_t i = lo + (int64_t)threadIdx.x * V; i < hi; i += (int64_t)LB * V) {
     float v[V];
-    ldv<V>(p + i, v);
+    hd_ldv<V>(p + i, v);
 #pragma unroll
     for (int e = 0; e < V; ++e) {
       mn = fminf(mn, v[e]);
       mx = fmaxf(mx, v[e]);
     }
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    mn = fminf(mn, __shfl_xor(mn, d));
-    mx = fmaxf(mx, __shfl_xor(mx, d));
-  }
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    sm[w * 2] = mn;
-    sm[w * 2 + 1] = mx;
-  }
-  __syncthreads();
+  hd_wave_reduce2(mn, HdMin(), mx, HdMax());
+  const float mm[2] = {mn, mx};
+  hd_block_put(mm, sm);
   if (threadIdx.x == 0) {
     mn = fminf(fminf(sm[0], sm[2]), fminf(sm[4], sm[6]));
     mx = fmaxf(fmaxf(sm[1], sm[3]), fmaxf(sm[5], sm[7]));
@@ -175,8 +150,8 @@ __global__ __launch_bounds__(LB) void media_render_kernel(RenderArgs a) {
         const int k = gy * a.xmaps + j0 + j;
         if (k < a.N) {
           const float2 m = a.part[((int64_t)k * a.PC + c) * a.B + b];
-          atomicMin(&smn[j * 3 + c], f2key(m.x));
-          atomicMax(&smx[j * 3 + c], f2key(m.y));
+          atomicMin(&smn[j * 3 + c], hd_float_key(m.x));
+          atomicMax(&smx[j * 3 + c], hd_float_key(m.y));
         }
       }
       __syncthreads();
@@ -200,10 +175,10 @@ __global__ __launch_bounds__(LB) void media_render_kernel(RenderArgs a) {
       for (int c = 0; c < 3; ++c) {
         if (c == 0 || a.sc != 0) {                             // a stride-0 channel view: one load, one conversion
           float v[V];
-          ldv<V>(p + c * a.sc, v);
+          hd_ldv<V>(p + c * a.sc, v);
           if constexpr (MODE == HD_MEDIA_NORMALISE) {
             const int kc = j * 3 + (a.PC == 3 ? c : 0);
-            const float mn = key2f(smn[kc]), mx = key2f(smx[kc]);
+            const float mn = hd_key_float(smn[kc]), mx = hd_key_float(smx[kc]);
             const float rng = mx - mn;
 #pragma unroll
             for (int e = 0; e < V; ++e) {
@@ -283,7 +258,6 @@ __global__ __launch_bounds__(LB) void media_render_kernel(RenderArgs a) {
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -340,7 +314,7 @@ extern "C" int hd_media_render(const float* x, int64_t stride_n, int64_t stride_
   a.gb = gt_boxes; a.gc = gt_count; a.Q = Q;
   a.canvas = canvas;
   // 16-byte loads need every image row to start on a 16-byte boundary
-  const bool vec = (W % 4) == 0 && (stride_n % 4) == 0 && (stride_c % 4) == 0 && aligned16(x);
+  const bool vec = (W % 4) == 0 && (stride_n % 4) == 0 && (stride_c % 4) == 0 && hd_aligned16(x);
   if (norm) {
     const int64_t chunk = (((HW + B - 1) / B) + 3) & ~(int64_t)3;
     const dim3 grid(B, N * a.PC);

@@ -8,28 +8,12 @@
 // One thread owns a position (n, o) of an image plane and walks the three channels there: the IR plane is read once, contiguously.
 // Sums are two-stage (fixed block partials, then one block in index order): deterministic, no atomics.  Every mode evaluates the
 // same per-element expressions in the same order, so value-only and gradient calls, eager and captured, agree bit for bit.
-#include "hd_common.h"
+#include "hd_block.h"
 
 namespace {
 
 constexpr int LB = 256;        // threads per block
 constexpr int NPART = 1024;    // most partial-sum blocks (part_ws holds 2 * NPART floats)
-
-__device__ __forceinline__ void block_sum2(float& a, float& b, float* sm) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    a += __shfl_xor(a, d);
-    b += __shfl_xor(b, d);
-  }
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    sm[w * 2] = a;
-    sm[w * 2 + 1] = b;
-  }
-  __syncthreads();
-  a = sm[0] + sm[2] + sm[4] + sm[6];
-  b = sm[1] + sm[3] + sm[5] + sm[7];
-}
 
 template <int KIND>
 __device__ __forceinline__ float pix_value(float d) {
@@ -39,27 +23,6 @@ __device__ __forceinline__ float pix_value(float d) {
 template <int KIND>
 __device__ __forceinline__ float pix_dir(float d) {
   return KIND == 0 ? d : (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f));
-}
-
-// V consecutive floats of one plane: one 16-byte load / store (V = 4) or one scalar (V = 1)
-template <int V>
-__device__ __forceinline__ void ldv(const float* p, float (&v)[V]) {
-  if constexpr (V == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = *p;
-  }
-}
-template <int V>
-__device__ __forceinline__ void stv(float* p, const float (&v)[V]) {
-  if constexpr (V == 4) {
-    f32x4 t;
-    t.x = v[0]; t.y = v[1]; t.z = v[2]; t.w = v[3];
-    *reinterpret_cast<f32x4*>(p) = t;
-  } else {
-    *p = v[0];
-  }
 }
 
 // positions q = n * PV + o, PV = H*W / V; channel c of image n is vector (n*3 + c)*PV + o of hall / rgb (and of a three-plane ir),
@@ -78,14 +41,14 @@ __global__ __launch_bounds__(LB) void pixel_loss_kernel(const float* __restrict_
     const int64_t n = q / PV;
     const int64_t o = q - n * PV;
     float iv[V];
-    if constexpr (!IR3) ldv<V>(ir + (n * PV + o) * V, iv);
+    if constexpr (!IR3) hd_ldv<V>(ir + (n * PV + o) * V, iv);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const int64_t e = ((n * 3 + c) * PV + o) * V;
       float h[V], r[V];
-      ldv<V>(hall + e, h);
-      ldv<V>(rgb + e, r);
-      if constexpr (IR3) ldv<V>(ir + e, iv);
+      hd_ldv<V>(hall + e, h);
+      hd_ldv<V>(rgb + e, r);
+      if constexpr (IR3) hd_ldv<V>(ir + e, iv);
       float dg[V];
 #pragma unroll
       for (int k = 0; k < V; ++k) {
@@ -100,14 +63,14 @@ __global__ __launch_bounds__(LB) void pixel_loss_kernel(const float* __restrict_
       }
       if constexpr (GRAD) {
         float old[V];
-        ldv<V>(dhall + e, old);
+        hd_ldv<V>(dhall + e, old);
 #pragma unroll
         for (int k = 0; k < V; ++k) old[k] = old[k] + dg[k];
-        stv<V>(dhall + e, old);
+        hd_stv<V>(dhall + e, old);
       }
     }
   }
-  block_sum2(sr, si, sm);
+  hd_block_sum2<LB / 64>(sr, si, sm);
   if (threadIdx.x == 0) {
     part[blockIdx.x * 2] = sr;
     part[blockIdx.x * 2 + 1] = si;
@@ -123,7 +86,7 @@ __global__ __launch_bounds__(LB) void pixel_loss_finish_kernel(const float* __re
     a += part[i * 2];
     b += part[i * 2 + 1];
   }
-  block_sum2(a, b, sm);
+  hd_block_sum2<LB / 64>(a, b, sm);
   if (threadIdx.x == 0) {
     const float lr = w_rgb * (a / nf), li = w_ir * (b / nf);
     out[0] = lr;
@@ -157,8 +120,6 @@ void launch_k(bool ir3, bool grad, bool vec, int grid, hipStream_t s, const floa
   }
 }
 
-inline bool aligned16(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" int hd_pixel_loss(const float* hall, const float* rgb, const float* ir, int N, int C, int H, int W, int ir_channels, float w_rgb,
@@ -173,7 +134,7 @@ extern "C" int hd_pixel_loss(const float* hall, const float* rgb, const float* i
   const int64_t P = (int64_t)H * W;
   const int64_t n = (int64_t)N * 3 * P;
   // 16-byte accesses need every plane to start on a 16-byte boundary: H*W a multiple of 4 and 16-byte aligned bases
-  const bool vec = (P % 4) == 0 && aligned16(hall) && aligned16(rgb) && aligned16(ir) && aligned16(dhall);
+  const bool vec = (P % 4) == 0 && hd_aligned16(hall) && hd_aligned16(rgb) && hd_aligned16(ir) && hd_aligned16(dhall);
   const int64_t positions = (int64_t)N * (vec ? P / 4 : P);
   int64_t g = (positions + LB - 1) / LB;
   const int grid = (int)(g > NPART ? NPART : g);

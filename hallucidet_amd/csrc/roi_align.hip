@@ -1,7 +1,7 @@
 // RoIAlign (aligned=False) forward / backward, single- and multi-level (torchvision.ops.roi_align / MultiScaleRoIAlign [EXT], reached from
 // src/utils/eval_forward_fasterrcnn.py:120-123 `box_roi_pool`).  The only detection kernels that touch ACTIVATIONS: this file is built
 // twice (fp16 storage, and -DHD_STORE_F32 for precision=32: entry points with the suffix _f32); box maths in fp32 either way.
-#include "hd_common.h"
+#include "hd_block.h"
 #pragma clang fp contract(off)
 
 namespace {
@@ -404,7 +404,7 @@ __device__ __forceinline__ GatherTile gather_tile(const MLFeat& ml, int L, int4 
 template <int NT, int PH, int PW, int SR>
 __device__ __forceinline__ int gather_list(const MLFeat& ml, const float* __restrict__ rois, const int* __restrict__ level, int R, int base,
                                            const GatherTile& t, GatherRoi* list, int* wcnt) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   int total = 0;
   for (int it = 0; it < GATHER_CAP / NT; ++it) {
     const int r = base + it * NT + tid;
@@ -419,16 +419,9 @@ __device__ __forceinline__ int gather_list(const MLFeat& ml, const float* __rest
         e.y0 = (short)g.y0; e.y1 = (short)y1; e.x0 = (short)g.x0; e.x1 = (short)x1;
       }
     }
-    const unsigned long long m = __ballot(hit);
-    if (lane == 0) wcnt[wave] = __popcll(m);
-    __syncthreads();
-    int off = total, all = 0;
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) {
-      if (w < wave) off += wcnt[w];
-      all += wcnt[w];
-    }
-    if (hit) list[off + __popcll(m & ((1ull << lane) - 1ull))] = e;
+    int all;
+    const int rank = total + hd_block_rank<NT / 64>(hit, wcnt, &all);
+    if (hit) list[rank] = e;
     total += all;
     __syncthreads();
   }

@@ -21,7 +21,7 @@
 // gradient call evaluate the same expressions (the file is built without contraction), so their out bits agree.
 #include <math.h>
 
-#include "hd_common.h"
+#include "hd_block.h"
 
 namespace {
 
@@ -42,22 +42,6 @@ static_assert(4 * (CG - 1) + 16 <= IWP, "the horizontal pass reads 16 staged flo
 struct Win {
   float g[WIN];
 };
-
-__device__ __forceinline__ void block_sum2(float& a, float& b, float* sm) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    a += __shfl_xor(a, d);
-    b += __shfl_xor(b, d);
-  }
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    sm[w * 2] = a;
-    sm[w * 2 + 1] = b;
-  }
-  __syncthreads();
-  a = sm[0] + sm[2] + sm[4] + sm[6];
-  b = sm[1] + sm[3] + sm[5] + sm[7];
-}
 
 // dst[row][col] = plane[y0 + row][x0 + col] where lo <= y < H and lo <= x < W, else 0; rows 0..IH-1, columns 0..IWP-1.
 // VEC: W % 4 == 0, x0 % 4 == 0 and a 16-byte aligned plane: one 16-byte load per four columns that lie inside the row.
@@ -231,7 +215,7 @@ __global__ __launch_bounds__(NT) void ssim_fwd_kernel(const float* __restrict__ 
       }
     }
   }
-  block_sum2(sr, si, s_red);
+  hd_block_sum2<NT / 64>(sr, si, s_red);
   if (threadIdx.x == 0) {
     const int64_t b = ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     part[b * 2] = sr;
@@ -248,7 +232,7 @@ __global__ __launch_bounds__(NT) void ssim_finish_kernel(const float* __restrict
     a += part[i * 2];
     b += part[i * 2 + 1];
   }
-  block_sum2(a, b, sm);
+  hd_block_sum2<NT / 64>(a, b, sm);
   if (threadIdx.x == 0) {
     const float qr = a / nf, qi = b / nf;
     const float lr = w_rgb * (1.f - qr), li = w_ir * (1.f - qi);
@@ -297,8 +281,6 @@ __global__ __launch_bounds__(NT) void ssim_bwd_kernel(const float* __restrict__ 
     }
   }
 }
-
-inline bool aligned16(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 inline int64_t part_floats(int N, int H, int W) {
   const int64_t nb = (int64_t)N * hd_cdiv(H - R, TH) * hd_cdiv(W - R, TW);
@@ -356,7 +338,7 @@ extern "C" int hd_ssim_loss(const float* hall, const float* rgb, const float* ir
   const bool grad = dhall != nullptr;
   const int64_t need = hd_ssim_loss_workspace(N, H, W, grad ? 1 : 0);
   HD_CHECK_ARG(ws_bytes >= need, "hd_ssim_loss: workspace too small (%lld bytes given, %lld needed)", (long long)ws_bytes, (long long)need);
-  HD_CHECK_ARG(aligned16(ws), "hd_ssim_loss: the workspace must be 16-byte aligned");
+  HD_CHECK_ARG(hd_aligned16(ws), "hd_ssim_loss: the workspace must be 16-byte aligned");
   static const Win w = make_window();
   const int Hm = H - R, Wm = W - R;
   const int64_t cnt = (int64_t)N * 3 * Hm * Wm;
@@ -366,7 +348,7 @@ extern "C" int hd_ssim_loss(const float* hall, const float* rgb, const float* ir
   float* pws = part + part_floats(N, H, W);
   // 16-byte accesses need every row of every plane on a 16-byte boundary: W a multiple of 4 and aligned bases (tiles start at
   // multiples of TW)
-  const bool vec = (W % 4) == 0 && aligned16(hall) && aligned16(rgb) && aligned16(ir);
+  const bool vec = (W % 4) == 0 && hd_aligned16(hall) && hd_aligned16(rgb) && hd_aligned16(ir);
   const bool ir3 = ir_channels == 3;
   hipStream_t s = (hipStream_t)stream;
   const dim3 gf(hd_cdiv(Wm, TW), hd_cdiv(Hm, TH), N);

@@ -12,7 +12,7 @@ and the element-wise focal kernel 2 048 x 256 = 524 288, RetinaNet forward 32 x 
 256 x 256 = 65 536, Adam 4 096 x 256 x 4 = 4 194 304, check_finite 2 048 x 256 = 524 288.
 
 Tolerances.  U32, SCALAR_RTOL, REDUCE_RTOL and worst_ratio are _bn_reference's; LOSS_RTOL, LOSS_FLOOR and the focal `mag` expressions are
-_fcos_reference's (losses.hip's focal_terms / focal_value / focal_grad are textually fcos.hip's), and LOSS_RTOL also bounds the RPN's
+_fcos_reference's (losses.hip and fcos.hip share ONE focal_terms / focal_value / focal_grad: csrc/hd_det_math.h), and LOSS_RTOL also bounds the RPN's
 BCE-with-logits, which is the focal loss's `ce` term: |got - ref| <= RTOL*mag + LOSS_FLOOR.  `mag` is the first-order error magnitude:
 the sum of the absolute values of the terms, a difference counting BOTH operands.  Three constants are new.  Each is 4x the worst
 (|err| - LOSS_FLOOR) / mag of a numpy float32 evaluation of the defining formulas (ATen's smooth_l1 / log_softmax and torch.optim.Adam's,
