@@ -18,6 +18,9 @@ def main(argv=None):
     if args.augment != "none":
         raise SystemExit("eval_hallucidet.py: --augment %s is an option of train_detector.py (evaluation reads the raw images); use "
                          "--augment none" % args.augment)
+    if args.augment_geometry != "none":
+        raise SystemExit("eval_hallucidet.py: --augment-geometry %s is an option of the training scripts (evaluation reads the raw images); "
+                         "use --augment-geometry none" % args.augment_geometry)
     torch.manual_seed(args.seed)
     dataset = args.dataset or "llvip"
     Config.set_detector(args.detector, train_det=False, pretrained=args.directly_coco, dataset=dataset)

@@ -171,6 +171,8 @@ PROTOTYPES = {
     "hd_augment_u8_ws_bytes": (c_i64, [C.c_int] * 4),
     "hd_augment_u8": (C.c_int, [vp, vp] + [C.c_int] * 4 + [vp, vp, vp]),
     "hd_batch_gather_u8": (C.c_int, [vp, c_i64, vp, C.c_int, c_i64, C.c_int, vp, vp]),
+    "hd_geometry_check_rows": (C.c_int, [vp] + [C.c_int] * 3),
+    "hd_geometry_u8": (C.c_int, [vp, c_i64, vp, vp] + [C.c_int] * 5 + [vp, vp]),
     "hd_ir_preprocess_ws_bytes": (c_i64, [C.c_int] * 5),
     "hd_ir_preprocess": (C.c_int, [vp] + [C.c_int] * 4 + [C.POINTER(C.c_int), C.c_int, vp, vp, vp, vp]),
     "hd_media_ws_bytes": (c_i64, [C.c_int]),

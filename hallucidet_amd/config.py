@@ -128,6 +128,12 @@ class Config:
         # train_detector.py: 'reference' = the reference's photometric augmentation of the training split (train_detector.py:401-410),
         # applied to the uint8 batch on the GPU (dataloader/augment.py)
         p.add_argument("--augment", type=str, default="none", choices=["none", "reference"])
+        # geometric augmentation of the training split on the GPU (dataloader/geometry.py, hd_geometry_u8): 'hflip' = horizontal flip
+        # with probability 0.5; 'hflip_crop' = also, with probability 0.5, a random crop that contains every box, no smaller than
+        # --geometry-min-scale of each side, resized back to the input's size.  Paired batches get one transform for both modalities
+        # and the boxes follow.  Validation and test are never augmented.  Default: off
+        p.add_argument("--augment-geometry", type=str, default="none", choices=["none", "hflip", "hflip_crop"])
+        p.add_argument("--geometry-min-scale", type=float, default=0.5, metavar="S")
         # the image-space IR pre-processing baselines of the reference (models/cnnBasedThermalInfraredDA.py), on the GPU: in
         # eval_hallucidet.py / train_hallucidet.py what the "RGB Detector on IR" pass reads in validation and test; in
         # train_detector.py --modality ir what the detector is fine-tuned and evaluated on
@@ -197,6 +203,15 @@ class Config:
         """The data modules' cache keywords from --cache-dataset / --cache-budget-gb."""
         budget = None if args.cache_budget_gb is None else int(args.cache_budget_gb * 1e9)
         return dict(cache=args.cache_dataset, cache_budget_bytes=budget, device=device)
+
+    @staticmethod
+    def train_geometry(args, rank=0):
+        """--augment-geometry / --geometry-min-scale -> the `PairedGeometry` of the training split, or None when off."""
+        if args.augment_geometry == "none":
+            return None
+        from .dataloader.geometry import PairedGeometry
+        return PairedGeometry(p_flip=0.5, p_crop=0.5 if args.augment_geometry == "hflip_crop" else 0.0, min_scale=args.geometry_min_scale,
+                              seed=args.seed, rank=rank)
 
     @staticmethod
     def set_loss_weights(args):

@@ -331,11 +331,18 @@ class DevicePrefetcher:
     vector travels through the pinned slots and `ops.batch_gather` builds the same float batch out of the cache's arena with one launch
     on the side stream (as uint8 when an augmentation follows); the targets travel exactly as above."""
 
-    def __init__(self, loader, device="cuda", augment=None):
+    def __init__(self, loader, device="cuda", augment=None, geometry=None):
         """augment: a `ReferenceAugmentation` (dataloader/augment.py) or None.  When given, single-modal batches are augmented as
         uint8, before the division by 255: the per-image parameter rows are drawn for (epoch, batch index), travel as one pinned copy
-        and `ops.augment_u8` runs on the staging stream (`apply_host` on a CPU device)."""
+        and `ops.augment_u8` runs on the staging stream (`apply_host` on a CPU device).
+        geometry: a `PairedGeometry` (dataloader/geometry.py) or None.  When given, the per-image records are drawn from the batch's
+        host targets for (epoch, batch index) and travel as one pinned copy; every image group of the batch (RGB and IR of a paired
+        one) is transformed with the same records by `ops.geometry_u8` on the staging stream -- an uploaded uint8 batch, or the cache's
+        arena directly for an index batch -- and the boxes are transformed on the host before their upload.  The kernel's float output
+        is the IEEE quotient b / 255; with `augment` as well the geometry yields uint8, the photometric set follows, then the IEEE
+        division.  On a CPU device `geometry.apply_host` computes the same bytes."""
         self.augment, self._batch, self._aug_ws = augment, -1, None
+        self.geometry = geometry
         self.loader, self.device = loader, torch.device(device)
         self.cuda = self.device.type == "cuda"
         if self.cuda and self.device.index is None:          # the staging thread needs the concrete device
@@ -377,11 +384,31 @@ class DevicePrefetcher:
                 u8 = torch.stack(seq)
             else:
                 u8 = self._upload(("img", g), seq, True)
+            if rows_host is not None:
+                if u8.dtype != torch.uint8:
+                    raise TypeError("DevicePrefetcher: the geometric augmentation takes uint8 images (got %s)" % u8.dtype)
+                if tuple(u8.shape[-2:]) != (H, W):
+                    raise ValueError("DevicePrefetcher: the geometric augmentation needs one image size per batch (%s and %s)"
+                                     % ((H, W), tuple(u8.shape[-2:])))
+                if not u8.is_cuda:
+                    from .geometry import apply_host as geometry_host
+                    u8 = geometry_host(u8, rows_host)
+                elif augment is None:
+                    return ops.geometry_u8(u8, rows_dev, mode="f32_ieee")
+                else:
+                    u8 = ops.geometry_u8(u8, rows_dev, mode="u8")
             return finish(g, u8, augment)
 
         def gathered(g, idx, idx_host, augment=None):
             """image group g of an IndexBatch (dataloader/cache.py): one gather launch out of the cache's arena on the staging stream"""
             arena = batch.cache.arenas[g]
+            if rows_host is not None:
+                if tuple(arena.shape[-2:]) != (H, W):
+                    raise ValueError("DevicePrefetcher: the geometric augmentation needs one image size per batch (%s and %s)"
+                                     % ((H, W), tuple(arena.shape[-2:])))
+                if augment is None:
+                    return ops.geometry_u8(arena, rows_dev, idx=idx, idx_host=idx_host, mode="f32_ieee")
+                return finish(g, ops.geometry_u8(arena, rows_dev, idx=idx, idx_host=idx_host, mode="u8"), augment)
             if augment is None:
                 return ops.batch_gather(arena, idx, "f32_default", idx_host=idx_host)
             return finish(g, ops.batch_gather(arena, idx, "u8", idx_host=idx_host), augment)
@@ -405,6 +432,8 @@ class DevicePrefetcher:
 
         def tgts(g, seq):
             seq = list(seq)
+            if rows_host is not None:
+                seq = transform_targets(rows_host, seq, H, W)
             out = [dict(t) for t in seq]
             keys = [k for k, v in seq[0].items() if torch.is_tensor(v)] if seq else []
             for k in keys:
@@ -420,6 +449,17 @@ class DevicePrefetcher:
             return out
         multi = "DevicePrefetcher: the augmentation is defined for single-modal (image, target) batches only; the reference's HalluciDet " \
                 "training has none"
+        rows_host = rows_dev = None
+        H = W = 0
+        if self.geometry is not None:
+            from .geometry import check_rows, transform_targets
+            if isinstance(batch, IndexBatch):
+                groups, (H, W) = batch.targets, batch.cache.arenas[0].shape[-2:]
+            else:
+                groups, (H, W) = [batch[i] for i in range(1, len(batch), 2)], batch[0][0].shape[-2:]
+            H, W = int(H), int(W)
+            rows_host = check_rows(self.geometry.params_for(groups, H, W, self._batch), len(groups[0]), H, W, "DevicePrefetcher")
+            rows_dev = self._upload(("geo", 0), [rows_host], False)
         if isinstance(batch, IndexBatch):
             if not self.cuda:
                 raise RuntimeError("DevicePrefetcher: an index batch of the HBM dataset cache can only be staged on the GPU")

@@ -1429,6 +1429,71 @@ def batch_gather(arena, idx, mode, out=None, idx_host=None, validate=True):
     return out
 
 
+GEOM_ROW = 8                                    # int32 per image in hd_geometry_u8's record (HD_GEOM_ROW)
+GEOM_MODES = {"u8": 0, "f32_ieee": 1}           # HD_GEOM_* modes of hd_geometry_u8
+GEOM_MAX_BATCH = 65535                          # HD_GEOM_MAX_BATCH
+GEOM_MAX_EXTENT = 16384                         # HD_GEOM_MAX_EXTENT
+
+
+def geometry_u8(src, rows, *, idx=None, idx_host=None, validate=True, mode="u8", out=None):
+    """hd_geometry_u8: horizontal flip + crop window resized back to H x W (bilinear, a magnification), the arithmetic written out in
+    dataloader/geometry.py, on uint8 images in HBM.  src: contiguous uint8 [N, C, H, W] (idx None: the batch itself), or an arena
+    [S, C, H, W] with `idx`, N slot numbers exactly as for `batch_gather` (host idx: validated and uploaded; device idx: validated from
+    `idx_host`, or validate=False).  rows: int32 [N, GEOM_ROW], one record per image; on the host they are validated against H and W
+    (ValueError) and uploaded, on the device they are taken as they are -- the kernel clamps every field to the image, so no content
+    reads or writes out of bounds.  mode 'u8' -> uint8 [N, C, H, W]; 'f32_ieee' -> float32, the bytes / tensor(255.0).
+    One launch on the current stream, no workspace, no host synchronisation."""
+    if mode not in GEOM_MODES:
+        raise ValueError("geometry_u8: mode must be one of %s (got %r)" % (sorted(GEOM_MODES), mode))
+    if not torch.is_tensor(src) or src.dim() != 4 or src.dtype != torch.uint8 or not src.is_contiguous() or src.numel() == 0:
+        raise ValueError("geometry_u8: src must be a non-empty contiguous uint8 [N or S, C, H, W] tensor (got %s %s)"
+                         % (getattr(src, "dtype", type(src)), tuple(getattr(src, "shape", ()))))
+    S, Cc, H, W = src.shape
+    if idx is None:
+        if idx_host is not None:
+            raise ValueError("geometry_u8: idx_host without idx")
+        N = S
+    else:
+        on_device = torch.is_tensor(idx) and idx.is_cuda
+        if on_device:
+            if idx.dim() != 1 or idx.dtype != torch.int64 or not idx.is_contiguous():
+                raise ValueError("geometry_u8: idx must be a contiguous 1-D int64 vector (got %s %s)" % (idx.dtype, tuple(idx.shape)))
+            if validate:
+                if idx_host is None:
+                    raise ValueError("geometry_u8: a device idx needs its host copy (idx_host=) for the validation, or validate=False")
+                if check_gather_indices(idx_host, S).numel() != idx.numel():
+                    raise ValueError("geometry_u8: idx_host has %d values, idx %d" % (len(idx_host), idx.numel()))
+        else:
+            idx_host = check_gather_indices(idx, S)
+        N = int(idx.numel()) if on_device else int(idx_host.numel())
+    if N < 1 or N > GEOM_MAX_BATCH or Cc not in (1, 3) or not (2 <= H <= GEOM_MAX_EXTENT and 2 <= W <= GEOM_MAX_EXTENT):
+        raise ValueError("geometry_u8: need 1 <= N <= %d, C in (1, 3), 2 <= H, W <= %d (got N=%d, C=%d, H=%d, W=%d)"
+                         % (GEOM_MAX_BATCH, GEOM_MAX_EXTENT, N, Cc, H, W))
+    if not torch.is_tensor(rows) or rows.dtype != torch.int32 or tuple(rows.shape) != (N, GEOM_ROW) or not rows.is_contiguous():
+        raise ValueError("geometry_u8: rows must be a contiguous int32 [%d, %d] tensor (got %s %s)"
+                         % (N, GEOM_ROW, getattr(rows, "dtype", type(rows)), tuple(getattr(rows, "shape", ()))))
+    if not rows.is_cuda:
+        from .dataloader.geometry import check_rows
+        check_rows(rows, N, H, W, "geometry_u8")
+    dtype = torch.uint8 if mode == "u8" else torch.float32
+    if out is not None and (not torch.is_tensor(out) or out.dtype != dtype or tuple(out.shape) != (N, Cc, H, W) or not out.is_contiguous()):
+        raise ValueError("geometry_u8: out must be a contiguous %s tensor of shape %s" % (dtype, (N, Cc, H, W)))
+    _need_cuda(src, out)
+    for t in (idx, rows, out):
+        if torch.is_tensor(t) and t.is_cuda and t.device != src.device:
+            raise ValueError("geometry_u8: src, idx, rows and out must live on one device")
+    if idx is not None and not on_device:
+        idx = idx_host.to(src.device, non_blocking=True)
+    if not rows.is_cuda:
+        rows = rows.to(src.device, non_blocking=True)
+    if out is None:
+        out = torch.empty((N, Cc, H, W), dtype=dtype, device=src.device)
+    elif out.data_ptr() < src.data_ptr() + src.numel() and src.data_ptr() < out.data_ptr() + out.numel() * out.element_size():
+        raise ValueError("geometry_u8: out overlaps src (a gather cannot run in place)")
+    check(_abi.load().hd_geometry_u8(ptr(src), S, ptr(idx), ptr(rows), N, Cc, H, W, GEOM_MODES[mode], ptr(out), _stream()), "hd_geometry_u8")
+    return out
+
+
 IRP_INVERT, IRP_STRETCH, IRP_EQUALIZE, IRP_BLUR = 0, 1, 2, 3     # HD_IRP_* operation codes of hd_ir_preprocess
 IRP_MAX_STAGES = 4
 IRP_MAX_PIXELS = 1 << 24          # largest H*W of hd_ir_preprocess: its quantile ranks are formed in fp32 (HD_IRP_MAX_PIXELS)

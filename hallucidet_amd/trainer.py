@@ -18,8 +18,9 @@ from .dataloader import DevicePrefetcher
 
 class Trainer:
     def __init__(self, max_epochs=10, limit_train_batches=1.0, dirpath=None, monitor="val_map", mode="max", early_stopping=None,
-                 device="cuda", log_every=50, log=print, train_augment=None):
+                 device="cuda", log_every=50, log=print, train_augment=None, train_geometry=None):
         self.train_augment = train_augment          # dataloader.augment.ReferenceAugmentation: the TRAINING batches only
+        self.train_geometry = train_geometry        # dataloader.geometry.PairedGeometry: the TRAINING batches only
         self.max_epochs, self.limit_train_batches = max_epochs, limit_train_batches
         self.dirpath, self.monitor, self.mode = dirpath, monitor, mode
         self.early_stopping = early_stopping
@@ -158,7 +159,9 @@ class Trainer:
             run, seen = 0.0, 0
             if self.train_augment is not None:
                 self.train_augment.set_epoch(epoch)
-            for i, batch in enumerate(DevicePrefetcher(train, self.device, augment=self.train_augment)):
+            if self.train_geometry is not None:
+                self.train_geometry.set_epoch(epoch)
+            for i, batch in enumerate(DevicePrefetcher(train, self.device, augment=self.train_augment, geometry=self.train_geometry)):
                 if i >= n_train:
                     break
                 loss = model.fit_step(batch, i)

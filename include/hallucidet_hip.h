@@ -595,6 +595,26 @@ int hd_augment_u8(const uint8_t* x, const float* params, int N, int C, int H, in
 #define HD_GATHER_F32_IEEE 2
 #define HD_GATHER_MAX_BATCH 65535
 int hd_batch_gather_u8(const uint8_t* arena, int64_t S, const int64_t* idx, int N, int64_t chw, int mode, void* out, void* stream);
+/* Paired geometric augmentation (csrc/geometry.hip, dataloader/geometry.py): horizontal flip + crop window resized back to H x W
+ * (bilinear, half-pixel centres, a magnification), one gather launch.  src [S][C][H][W] uint8, dense; with idx = NULL it is the batch
+ * itself (S == N, image n reads slot n), otherwise an arena and idx [N] int64 device slot numbers exactly as for hd_batch_gather_u8
+ * (duplicates allowed, 64-bit slot offset, a slot outside [0, S) writes nothing).  rows [N][HD_GEOM_ROW] int32 on the device, one per
+ * image: [flip, x0, y0, x1, y1, 0, 0, 0] with 0 <= x0 < x1 <= W, 0 <= y0 < y1 <= H; the exact arithmetic is written out at the top of
+ * csrc/geometry.hip.  The kernel clamps every field to H and W before use, so no row content reads outside src or writes outside out;
+ * hd_geometry_check_rows validates a HOST copy of the rows (HD_E_ARG names the first bad row).  mode:
+ *   HD_GEOM_U8        out [N][C][H][W] uint8 = the resampled bytes b;
+ *   HD_GEOM_F32_IEEE  out [N][C][H][W] fp32  = (float)b / 255.0f correctly rounded (HD_GATHER_F32_IEEE's value).
+ * 1 <= N <= HD_GEOM_MAX_BATCH, C in {1, 3}, 2 <= H, W <= HD_GEOM_MAX_EXTENT (2 W^2 stays inside int32).  One launch, no workspace, no
+ * atomics, no host synchronisation, one writer per output element, the same bits from run to run.  W % 16 == 0 with src and out
+ * 16-byte aligned stores 16 bytes per lane out of source rows staged in LDS; any other shape takes one value per lane. */
+#define HD_GEOM_ROW 8
+#define HD_GEOM_U8 0
+#define HD_GEOM_F32_IEEE 1
+#define HD_GEOM_MAX_BATCH 65535
+#define HD_GEOM_MAX_EXTENT 16384
+int hd_geometry_check_rows(const int32_t* rows, int N, int H, int W);
+int hd_geometry_u8(const uint8_t* src, int64_t S, const int64_t* idx, const int32_t* rows, int N, int C, int H, int W, int mode, void* out,
+                   void* stream);
 /* Image-space IR pre-processing baselines of the reference (src/models/cnnBasedThermalInfraredDA.py: invert, histogram stretching,
  * histogram equalization, 3 x 3 Gaussian blur and their chains) on a planar fp32 batch (csrc/ir_preprocess.hip).
  * x, out [N][C][H][W] fp32, C = 3 or 1, N*C <= 65535, H, W >= 2 (reflect padding), H*W <= HD_IRP_MAX_PIXELS (ranks are formed in

@@ -48,7 +48,7 @@ def main(argv=None):
         augment = ReferenceAugmentation(seed=args.seed, rank=rank)
     tr = Trainer(max_epochs=args.epochs, limit_train_batches=args.limit_train_batches, dirpath=out_dir if rank == 0 else None, monitor="val_map",
                  mode="max", early_stopping=("val_map", "max", 5), device=dev, log=print if rank == 0 else (lambda *a: None),
-                 train_augment=augment)
+                 train_augment=augment, train_geometry=Config.train_geometry(args, rank))
     tr.fit(model, dm)
     if rank == 0:
         res = tr.test(model, dm)

@@ -70,7 +70,8 @@ def main(argv=None):
     model.prepare()
     out_dir = os.path.join("lightning_logs", args.wandb_project, args.wandb_name)
     tr = Trainer(max_epochs=args.epochs, limit_train_batches=args.limit_train_batches, dirpath=out_dir if rank == 0 else None,
-                 monitor="map_hall/map_50", mode="max", device=dev, log=print if rank == 0 else (lambda *a: None))
+                 monitor="map_hall/map_50", mode="max", device=dev, log=print if rank == 0 else (lambda *a: None),
+                 train_geometry=Config.train_geometry(args, rank))
     tr.fit(model, dm)
     if rank == 0:
         tr.save_checkpoint(model, os.path.join(out_dir, "encoder_decoder_pl.ckpt"))
